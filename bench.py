@@ -31,12 +31,29 @@ Frames are enqueued back to back: per-launch statistics come back through a ring
 stalling the host between launches.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c3s|c3t|c2|c4|c5]
-       [--mode progressive|frame] [--dist-backend nccl|gloo] [--verify] [--secondary LIST]
+       [--mode progressive|frame] [--dist-backend nccl|gloo] [--verify] [--dump-outputs DIR]
+       [--full [--secondary LIST]]
        torchrun --nproc-per-node N bench.py --gpus N ...
 With --gpus N > 1 and no launcher (WORLD_SIZE unset) bench.py starts the N ranks itself
 (torch.distributed.run as a child process, before this process touches a GPU) and relays rank
-0's JSON line; under a launcher --gpus must equal WORLD_SIZE.  On one GPU with the default c3,
-the line also carries "secondary": C3t, C3s and C5 measured the same way with a few steps each.
+0's JSON line; under a launcher --gpus must equal WORLD_SIZE.
+
+A plain run does only what the headline figure needs: it builds the scene, renders the warmup
+steps, times the K steps, writes the last step's outputs if --dump-outputs is given, and
+prints the line (Mray/s, ms_per_step, the HIP-event kernel time of the timed launches).
+--full adds everything else, each in a run of its own after the timed region: the same steps
+rendered again with event counting on (samples and rays per frame, the HBM roofline), the
+same frames at one launch per frame ("single_frame_launches"), the CPU baselines, and -- on
+one GPU with the default c3 -- "secondary": C3t, C3s and C5 measured the same way with a few
+steps each.  --no-cpu-baseline, --no-single-compare and --secondary none take single legs out
+of a --full run.
+
+--dump-outputs DIR writes what the timed path left in its caller's buffers after the last
+timed step, as float32 .npy files: framebuffer_rgba8.npy (H, W, 4: the RGBA8 framebuffer's
+bytes) and, on one GPU, accum_rgba.npy (H, W, 4: the progressive accumulation buffer).  Above
+64 MB in all (c4) a fixed seeded sample of the pixels is written instead, (n, 4) each, with
+their row-major pixel numbers in pixel_index.npy (float64).  The inputs are synthetic and the
+seeds depend only on (accumID, W, H, x, y), so equal arguments give equal files.
 """
 import argparse
 import glob
@@ -223,6 +240,25 @@ def orbit_camera(k):
 # driver's clock too: terrain (the realistic-data layout), the sample-heavy TF and R2B09
 SECONDARY = ("c3t", "c3s", "c5")
 
+DUMP_BUDGET = 64 * 10**6  # bytes: all of --dump-outputs' files together
+
+
+def dump_outputs(path, W, H, arrays):
+    """Write `arrays` (name -> (W*H, C) array, row-major pixels) as float32 path/<name>.npy,
+    whole as (H, W, C) when they fit DUMP_BUDGET together, else the same seeded pixel sample
+    of each with the pixel numbers in pixel_index.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    per_pixel = sum(4 * a.shape[1] for a in arrays.values())
+    if W * H * per_pixel <= DUMP_BUDGET:
+        for name, a in arrays.items():
+            np.save(os.path.join(path, name + ".npy"), a.astype(np.float32).reshape(H, W, -1))
+        return
+    n = DUMP_BUDGET // (per_pixel + 8)
+    idx = np.sort(np.random.default_rng(0).choice(W * H, size=n, replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a[idx].astype(np.float32))
+    np.save(os.path.join(path, "pixel_index.npy"), idx.astype(np.float64))
+
 
 def spawn_ranks(n, argv):
     """`bench.py --gpus N` (N > 1) started as a plain program: one rank per GPU, launched as
@@ -266,7 +302,17 @@ def parse_args(argv=None):
     ap.add_argument("--mode", default="progressive", choices=["progressive", "frame"],
                     help="progressive: N frames per step (weak); frame: one frame per step "
                          "split over the N ranks (strong)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also: the counted re-run of the timed steps "
+                         "(samples per frame, roofline), the one-launch-per-frame comparison, the "
+                         "CPU baselines and the secondary configs.  Off: the plain run (set up, "
+                         "warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the framebuffer (and on one GPU the accumulation buffer) as the "
+                         "last timed step left them to DIR/<name>.npy (float32; at most 64 MB in "
+                         "all, a fixed seeded pixel sample beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baselines")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--sampler", default="user", choices=["user", "tri", "cubql"],
                     help="Volume::mode (Params.h:29-31): sample() on the cells (default), "
@@ -280,15 +326,16 @@ def parse_args(argv=None):
     ap.add_argument("--stats", default="off", choices=["on", "off"],
                     help="per-launch event counts (irt_set_statistics) inside the timed loop.  "
                          "off (default): the product renders without them, as the reference "
-                         "does; the counts the roofline needs come from rendering the same "
-                         "steps again afterwards with counting on (untimed, identical frames)")
+                         "does; with --full the counts the roofline needs come from rendering "
+                         "the same steps again afterwards with counting on (untimed, identical "
+                         "frames)")
     ap.add_argument("--batch", type=int, default=8,
                     help="progressive frames per launch on one GPU (irt_render_accumulate: the "
                          "reference's accumulation loop over accumID, frames chained in one "
                          "launch; every frame's accum and fb are written). 1: one launch per frame")
     ap.add_argument("--no-single-compare", action="store_true",
-                    help="skip timing the same frames at one launch per frame after the timed "
-                         "region (profiling runs: one launch shape per kernel trace)")
+                    help="--full without timing the same frames at one launch per frame after "
+                         "the timed region (profiling runs: one launch shape per kernel trace)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearse the multi-rank path with host-staged collectives "
                          "(ranks may share a GPU); nccl (RCCL) is the measured path")
@@ -297,8 +344,8 @@ def parse_args(argv=None):
                          "sequence on its own context with irt_render_accumulate and compares "
                          "the assembled framebuffer pixel for pixel (exit 3 on a mismatch)")
     ap.add_argument("--secondary", default="auto",
-                    help="comma-separated configs measured after the primary line on one GPU "
-                         "(a few steps each, reported under \"secondary\"); auto: "
+                    help="with --full: comma-separated configs measured after the primary line "
+                         "on one GPU (a few steps each, reported under \"secondary\"); auto: "
                          + ",".join(SECONDARY) + " when the primary config is c3; none: skip")
     ap.add_argument("--secondary-steps", type=int, default=10)
     return ap.parse_args(argv)
@@ -433,7 +480,16 @@ def run_config(args, config, steps, warmup, rank, world, dist_path, primary=True
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_start
     tot, launches = ctx.stats_total()  # kernel time of the timed launches (HIP events)
-    if args.stats == "off":
+    if args.dump_outputs and primary and rank == 0:
+        # the caller's buffers as the last timed step left them (before anything below
+        # renders into them again)
+        arrays = {"framebuffer_rgba8": fb.cpu().numpy().view(np.uint8).reshape(-1, 4)}
+        if not dist_path:
+            arrays["accum_rgba"] = accum.cpu().numpy().reshape(-1, 4)
+        dump_outputs(args.dump_outputs, W, H, arrays)
+    recount = args.full and args.stats == "off"
+    counted_run = recount or args.stats == "on"  # the event counts below are there
+    if recount:
         # the event counts of the same steps (same accumIDs and cameras: identical frames and
         # counts), rendered again with counting on, untimed
         ctx.reset_stats_total()
@@ -455,7 +511,7 @@ def run_config(args, config, steps, warmup, rank, world, dist_path, primary=True
         ref_fb = torch.zeros(W * H, dtype=torch.int32, device=dev)
         ref_acc = torch.zeros(W * H * 4, dtype=torch.float32, device=dev)
         runs = [(0, (warmup + steps) * frames)]
-        if args.stats == "off":
+        if recount:
             runs.append((warmup * frames, steps * frames))
         q = irt.LaunchParams.from_buffer_copy(lp)
         for first, count in runs:
@@ -470,7 +526,7 @@ def run_config(args, config, steps, warmup, rank, world, dist_path, primary=True
                              "same accumID sequence"}
         log(f"[rank 0] verify: {bad} of {W * H} pixels differ from the single-context frame")
     single = None
-    if not dist_path and frames > 1 and not args.no_single_compare:
+    if args.full and not dist_path and frames > 1 and not args.no_single_compare:
         # the same workload at one launch per frame (irt_render), for comparison: the frames
         # that follow the timed steps' accumulation, statistics as in the timed loop
         ctx.set_statistics(args.stats == "on")
@@ -567,38 +623,41 @@ def run_config(args, config, steps, warmup, rank, world, dist_path, primary=True
                 "parallelism": parallelism,
                 "frames_per_step": frames,
                 "ms_per_frame": round(elapsed / (steps * frames) * 1e3, 4),
-                "samples_per_frame": samples_all / steps / frames,
-                "rays_in_box_per_frame": in_box_all / steps / frames,
-                "candidates_per_sample": tot.candidatesTested / max(samples, 1),
                 "kernel_ms_rank0": round(avg_kernel_s * 1e3, 4),
                 "statistics_in_timed_loop": args.stats,
                 "frames_per_launch": frames,
-                "bytes_per_launch_rank0": bytes_per_launch,
                 "chain_timeouts": chain_timeouts,
                 # the slot table (built when the headers outgrow the last-level cache)
                 "slot_table_bytes": ctx.array_bytes("slots"),
                 "context_create_s": round(create_s, 2),
             },
-            "roofline": {
+        }
+        if counted_run:  # what the event counts give (--full's counted re-run, or --stats on)
+            out["config"].update({
+                "samples_per_frame": samples_all / steps / frames,
+                "rays_in_box_per_frame": in_box_all / steps / frames,
+                "candidates_per_sample": tot.candidatesTested / max(samples, 1),
+                "bytes_per_launch_rank0": bytes_per_launch,
+            })
+            out["roofline"] = {
                 "bound": "hbm",
                 "achieved": round(achieved / 1e9, 3),
                 "peak": HBM_PEAK / 1e9,
                 "unit": "GB/s",
                 "frac": achieved / HBM_PEAK,
                 "traffic": None,
-            },
-        }
+            }
+            prof = profiled_traffic(f"k_render<{irt.default_kernel_id(ctx)}>", config, frames)
+            if prof and world == 1:
+                out["roofline"]["traffic"] = prof[0]
+                out["roofline"]["traffic_source"] = (
+                    f"{prof[1]}: rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE per launch "
+                    f"of the same kernel and workload")
         if single is not None:
             out["single_frame_launches"] = single  # the same frames, one launch each
         if verify is not None:
             out["verify"] = verify
-        prof = profiled_traffic(f"k_render<{irt.default_kernel_id(ctx)}>", config, frames)
-        if prof and world == 1:
-            out["roofline"]["traffic"] = prof[0]
-            out["roofline"]["traffic_source"] = (
-                f"{prof[1]}: rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE per launch "
-                f"of the same kernel and workload")
-        if primary and world == 1 and not args.no_cpu_baseline:
+        if args.full and primary and world == 1 and not args.no_cpu_baseline:
             cam = orbit_camera(0) if orbit is not None else FRAMING
             out["cpu_baseline"] = cpu_baseline(rn, bis, L, W, H, cam, tf, args.cpu_budget, terrain)
     if dist_path:
@@ -669,7 +728,7 @@ def main():
     torch.cuda.set_device(device)
 
     out = run_config(args, args.config, args.steps, args.warmup, rank, world, dist_path)
-    if out is not None and not dist_path:
+    if out is not None and not dist_path and args.full:
         names = ([] if args.secondary == "none" else
                  list(SECONDARY) if args.secondary == "auto" and args.config == "c3" else
                  [] if args.secondary == "auto" else args.secondary.split(","))

@@ -10,10 +10,10 @@ mkdir -p "$OUT"
 cd /tmp
 export TMPDIR=/tmp
 timeout -s KILL 200 rocprofv3 --kernel-trace --pmc TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_DRAM_sum \
-  --output-format csv -d "$OUT/req" -o run -- python3 "$ROOT/bench.py" --config "$CFG" --steps 20 --warmup 2 --no-cpu-baseline --no-single-compare \
+  --output-format csv -d "$OUT/req" -o run -- python3 "$ROOT/bench.py" --full --config "$CFG" --steps 20 --warmup 2 --no-cpu-baseline --no-single-compare \
   > "$OUT/bench.json" 2> "$OUT/bench.err"
 timeout -s KILL 200 rocprofv3 --kernel-trace --pmc TCC_EA0_WRREQ_64B_sum TCC_EA0_WRREQ_sum \
-  --output-format csv -d "$OUT/wr" -o run -- python3 "$ROOT/bench.py" --config "$CFG" --steps 20 --warmup 2 --no-cpu-baseline --no-single-compare \
+  --output-format csv -d "$OUT/wr" -o run -- python3 "$ROOT/bench.py" --full --config "$CFG" --steps 20 --warmup 2 --no-cpu-baseline --no-single-compare \
   > /dev/null 2>> "$OUT/bench.err" || echo "write-request pass failed" >&2
 python3 - "$OUT" <<'PY'
 import csv, glob, json, sys, collections

@@ -17,7 +17,7 @@ i=0
 for G in "${GROUPS_[@]}"; do
   i=$((i+1))
   timeout -s KILL 90 rocprofv3 --kernel-trace --pmc $G --output-format csv -d "$OUT/g$i" -o run \
-    -- python3 "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu-baseline "$@" > "$OUT/g$i.json" 2> "$OUT/g$i.err"
+    -- python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline "$@" > "$OUT/g$i.json" 2> "$OUT/g$i.err"
 done
 python3 "$ROOT/profiles/pmc_table.py" "$OUT" "g" > "$OUT/table.txt"
 cat "$OUT/table.txt"

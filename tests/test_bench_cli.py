@@ -35,3 +35,36 @@ def test_gpus_spawns_ranks():
     assert "2 RCCL ranks need 2 GPUs" in r.stderr
     assert r.returncode != 0
     assert r.stdout.strip() == ""
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs' writer: float32 files, whole frames while they fit the byte budget,
+    otherwise the same seeded pixel sample of every array (with the pixel numbers) that stays
+    within the budget and is identical from call to call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    W, H = 48, 32
+    rng = np.random.default_rng(1)
+    arrays = {"framebuffer_rgba8": rng.integers(0, 256, (W * H, 4), dtype=np.uint8),
+              "accum_rgba": rng.random((W * H, 4), dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / "whole"), W, H, arrays)
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "whole" / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == (H, W, 4)
+        assert np.array_equal(got.reshape(-1, 4), a.astype(np.float32))
+    assert not (tmp_path / "whole" / "pixel_index.npy").exists()
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), W, H, arrays)
+    idx = np.load(tmp_path / "s1" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and idx[-1] < W * H
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "s1").iterdir()) <= 4000
+    assert len(idx) == 4000 // 40
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "s1" / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == (len(idx), 4)
+        assert np.array_equal(got, a[idx.astype(np.int64)].astype(np.float32))
+        assert np.array_equal(got, np.load(tmp_path / "s2" / (name + ".npy")))
