@@ -1512,6 +1512,19 @@ int oracle_wedge_sample(const oc_cell *cells, size_t n, oc_vec3 p, float *value)
   return sampleVolume(S, toV3(p), *value);
 }
 
+int oracle_sample_volume(const oc_cell *cells, size_t n, int fast, const float *pts, int npts,
+                         int32_t *found, float *value) {
+  if (fast < 0 || fast > 2 || npts < 0) return -1;
+  Scene S{cells, n, fast, {}, {}, {}, false, {}, {}, false};
+  prepare(S, nullptr, 1);
+  for (int k = 0; k < npts; ++k) {
+    float v = 0.f;
+    found[k] = sampleVolume(S, V3{pts[3 * k], pts[3 * k + 1], pts[3 * k + 2]}, v) ? 1 : 0;
+    value[k] = found[k] ? v : 0.f;
+  }
+  return 0;
+}
+
 int oracle_triangle_sample(const oc_cell *cells, size_t n, oc_vec3 p, float *value) {
   Scene S{cells, n, 0, {}, {}, {}, false, {}, {}, true};
   buildTriangles(S);

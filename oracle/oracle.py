@@ -101,6 +101,7 @@ def olib() -> C.CDLL:
         L.oracle_intersect_wedge.argtypes = [P, OVec3, C.POINTER(C.c_float)]
         L.oracle_wedge_sample.argtypes = [P, S, OVec3, C.POINTER(C.c_float)]
         L.oracle_triangle_sample.argtypes = [P, S, OVec3, C.POINTER(C.c_float)]
+        L.oracle_sample_volume.argtypes = [P, S, I, P, I, P, P]
         L.oracle_linear_to_srgb.argtypes = [F]
         L.oracle_linear_to_srgb.restype = F
         L.oracle_make_rgba.argtypes = [P]
@@ -134,6 +135,9 @@ def rlib() -> C.CDLL:
         L.ref_lcg.argtypes = [C.c_uint, C.c_uint, I, P]
         L.ref_sample.argtypes = [P, P, C.POINTER(C.c_float)]
         L.ref_find_height.argtypes = [P, F]
+        # newer export (fixture generation only): a library built from an older harness lacks it
+        if hasattr(L, "ref_sample_volume"):
+            L.ref_sample_volume.argtypes = [P, I, P, I, P, P, P]
         L.ref_intersect_sphere.argtypes = [P, P, F, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.ref_box_test.argtypes = [P, P, F, F, P, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.ref_sdda_trace.argtypes = [P, P, F, F, P, P, I, P, P, P]
@@ -324,6 +328,34 @@ class TimedScene:
         if self._h:
             olib().oracle_scene_free(self._h)
             self._h = None
+
+
+def sample_volume(cells: np.ndarray, pts: np.ndarray, fast: int = 1):
+    """sampleVolume (the cell sampler) at pts (n,3) on the oracle; fast as OracleScene.render:
+    0 literal, 1 the scan, 2 the direction-voxel locator.  Returns (found int32, value float32)."""
+    cells = np.ascontiguousarray(cells, dtype=CELL_DTYPE)
+    pts = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+    found = np.zeros(len(pts), np.int32)
+    value = np.zeros(len(pts), np.float32)
+    rc = olib().oracle_sample_volume(_p(cells), cells.size, fast, _p(pts), len(pts), _p(found),
+                                     _p(value))
+    assert rc == 0
+    return found, value
+
+
+def ref_sample_volume(cells: np.ndarray, pts: np.ndarray):
+    """The reference's CPU sampleVolume loop (oracle/_ref) at pts (n,3); returns (found int32,
+    value float32, winning record index int32, -1 on a miss)."""
+    cells = np.ascontiguousarray(cells, dtype=CELL_DTYPE)
+    pts = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+    found = np.zeros(len(pts), np.int32)
+    value = np.zeros(len(pts), np.float32)
+    index = np.zeros(len(pts), np.int32)
+    if not hasattr(rlib(), "ref_sample_volume"):
+        raise RuntimeError("oracle/_ref/libiconref.so predates ref_sample_volume: make -C oracle ref")
+    rlib().ref_sample_volume(_p(cells), cells.size, _p(pts), len(pts), _p(found), _p(value),
+                             _p(index))
+    return found, value, index
 
 
 def ref_render(scene: OracleScene, params: OParams, width, height, rect=None, accum=None,

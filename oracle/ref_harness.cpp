@@ -550,6 +550,27 @@ int ref_sample(const void *cell, const float *pos3, float *value) {
   return ok;
 }
 int ref_find_height(const void *cell, float h) { return ((const ICONCell *)cell)->findHeight(h); }
+// The CPU sampleVolume loop (deviceCode.cu:119-122) over the reference's own sample(), for many
+// points per call: the lowest record index wins.  index[k] = the winning record, -1 on a miss.
+void ref_sample_volume(const void *cellsv, int n, const float *pts, int npts, int *found,
+                       float *value, int *index) {
+  const ICONCell *cells = (const ICONCell *)cellsv;
+  for (int k = 0; k < npts; ++k) {
+    const vec3f pos(pts[3 * k], pts[3 * k + 1], pts[3 * k + 2]);
+    float v = 0.f;
+    found[k] = 0;
+    value[k] = 0.f;
+    index[k] = -1;
+    for (unsigned i = 0; i < (unsigned)n; ++i) {
+      if (sample(cells[i], pos, v)) {
+        found[k] = 1;
+        value[k] = v;
+        index[k] = (int)i;
+        break;
+      }
+    }
+  }
+}
 int ref_intersect_sphere(const float *org3, const float *dir3, float radius, float *tn, float *tf) {
   Ray r(vec3f(org3[0], org3[1], org3[2]), vec3f(dir3[0], dir3[1], dir3[2]), 0.f, 1e10f);
   return intersectSphere(r, radius, *tn, *tf);

@@ -13,6 +13,12 @@ linear_to_srgb/make_rgba, toSpherical/toCartesian, getBounds, resampleLUT, Camer
 kats_grid.npz + f6_*_grid.npz the GRID_ACCEL_MODE path (dda3, buildGrid_ICON, a frame);
 kats_wedge.npz + f7_*_wedge.npz the CUBQL_MODE sampler (intersectWedgeEXT, the wedge
 sampleVolume, a frame).
+f8_terrain_*.npz + kats_terrain.npz (`make_golden.py terrain`, which writes these files only)
+pin the record layout convert_icon writes for real fields -- terrain-following heights, an
+inverted first layer over land (height[0] > height[1]), zero-thickness top records (65
+levels), voids under land: five frames of the reference raygen, and findHeight / sample /
+sampleVolume known answers at the radii where that layout is unobvious.  Thirteen golden
+frames in all (f1 x 2, f2..f7, f8 x 5) come from the reference's own code.
 The `.ic` inputs are synthetic grids from icon-ray-tracing_amd's generator (real DWD data
 is not available offline); they are stored verbatim, so the fixtures do not depend on it.
 """
@@ -24,7 +30,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [os.path.join(ROOT, "icon-ray-tracing_amd", "python"), os.path.join(ROOT, "oracle")]
+sys.path[:0] = [os.path.join(ROOT, "icon-ray-tracing_amd", "python"), os.path.join(ROOT, "oracle"),
+                os.path.join(ROOT, "tests")]
 
 import irt  # noqa: E402  (grid generator only)
 import oracle as O  # noqa: E402
@@ -32,7 +39,8 @@ import oracle as O  # noqa: E402
 FRAMING = irt.FRAMING_CAMERA
 
 FRAMES = {
-    # name: (rootN, bisections, levels, numCells cap, W, H, camera, accumIDs, raygen, tf)
+    # name: (rootN, bisections, levels, numCells cap, W, H, camera, accumIDs, raygen, tf
+    #        [, terrain: max HSURF in metres of irt.synth_grid(..., terrain=), default 0])
     "f1_ico12_viewall": (1, 0, 4, 12, 256, 256, None, (0,), 0, "default"),
     "f1_ico12_framing": (1, 0, 4, 12, 256, 256, FRAMING, (0,), 0, "default"),
     "f2_r2b02_l90": (2, 2, 90, -1, 128, 128, FRAMING, (0,), 0, "default"),
@@ -45,9 +53,10 @@ SPARSE_LUT5 = np.array([[0.1, 0.2, 0.9, 0.05], [0.9, 0.9, 0.2, 0.02], [0.8, 0.1,
                        np.float32)
 
 
-def make_frame(name, spec, mode=0):
-    rn, bis, L, cap, W, H, cam, ids, raygen, tf = spec
-    cells = irt.synth_grid(rn, bis, L, noise=0.1 if tf == "sparse" else 0.0)
+def make_frame(name, spec, mode=0, check=None):
+    rn, bis, L, cap, W, H, cam, ids, raygen, tf = spec[:10]
+    terrain = float(spec[10]) if len(spec) > 10 else 0.0
+    cells = irt.synth_grid(rn, bis, L, noise=0.1 if tf == "sparse" else 0.0, terrain=terrain)
     if cap >= 0:
         cells = cells[:cap].copy()  # --num-cells (hostCode.cu:112-113,728-730)
     S = O.OracleScene(cells)
@@ -98,13 +107,16 @@ def make_frame(name, spec, mode=0):
         p.accumID = aid
         _, _, c = O.ref_render(S, p, W, H, accum=accum, fb=fb, threads=1)
         counts.append(c.copy())
-    np.savez_compressed(
-        os.path.join(HERE, name + ".npz"), cells=cells.view(np.uint8).reshape(cells.size, 284),
+    out = dict(
+        cells=cells.view(np.uint8).reshape(cells.size, 284),
         width=W, height=H, camera12=cam12, accum_ids=np.array(ids, np.int32), raygen=raygen,
         lut=lut, value_range=np.array(vrange, np.float32), opacity_scale=np.float32(opacity),
         unit_distance=np.float32(unit_c), spherical_bounds=sb6, volume_bounds=vb6,
         data_range=dr, value_ranges=vr_ref, max_opacities=maxop, accum=accum, fb=fb,
         counts=np.array(counts, np.uint64), mode=mode)
+    if check is not None:
+        check(name, cells, out)  # before anything is written
+    np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
     print(f"{name}: {cells.size} records {W}x{H}, hit {(accum[..., 3] > 0).mean():.3f}, "
           f"samples {counts}")
 
@@ -398,9 +410,194 @@ def make_wedge_fixtures():
                mode=2)
 
 
+TERRAIN_FRAMES = {
+    "f8_terrain_r2b02_l90": (2, 2, 90, -1, 128, 128, FRAMING, (0,), 0, "default", 4000.0),
+    "f8_terrain_r2b02_l65_progressive": (2, 2, 65, -1, 96, 96, FRAMING, (0, 2, 3), 0, "default",
+                                         4000.0),
+    "f8_terrain_r2b01_l90_viewall": (2, 1, 90, -1, 96, 96, None, (0,), 0, "default", 4000.0),
+    "f8_terrain_r2b01_l90_ae": (2, 1, 90, -1, 64, 64, FRAMING, (0,), 1, "default", 4000.0),
+    "f8_terrain_r2b01_l65_sparse": (2, 1, 65, -1, 64, 64, FRAMING, (0,), 0, "sparse", 4000.0),
+}
+MAX_FIXTURE_BYTES = 1263401  # kats_grid.npz, the largest fixture before the terrain ones
+
+
+def check_terrain_frame(name, cells, out):
+    """The properties a terrain frame fixture exists for, asserted on the reference's data."""
+    nl = cells["numLayers"]
+    inverted = int(((nl > 0) & (cells["height"][:, 0] > cells["height"][:, 1])).sum())
+    zero = int((nl == 0).sum())
+    vr, mo = out["value_ranges"], out["max_opacities"]
+    inv_mc = int((vr[:, 1] < vr[:, 0]).sum())  # (FLT_MAX, -FLT_MAX): no record reached it
+    nonempty_zero_majorant = int(((vr[:, 1] >= vr[:, 0]) & (mo == 0)).sum())
+    counts = out["counts"]
+    voids = [int(c[0] - c[1]) for c in counts]
+    hit = float((out["accum"][..., 3] > 0).mean())
+    # pixels whose centre ray meets the scene's outer sphere: the most a frame can hit
+    c, W, H = out["camera12"].astype(np.float64), int(out["width"]), int(out["height"])
+    ys, xs = np.mgrid[0:H, 0:W]
+    d = c[3:6] + (xs[..., None] + 1.0) * c[6:9] + (ys[..., None] + 1.0) * c[9:12]
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    b = d @ c[0:3]
+    disc = float((b * b - (c[0:3] @ c[0:3] - float(out["spherical_bounds"][3]) ** 2) > 0).mean())
+    print(f"{name}: inverted records {inverted}, zero-thickness records {zero}, void samples "
+          f"{voids}, inverted macrocells {inv_mc}, non-empty macrocells with majorant 0 "
+          f"{nonempty_zero_majorant}, hit fraction {hit:.3f} (globe covers {disc:.3f})")
+    assert inverted >= 1, name
+    if "_l65" in name:
+        assert zero >= 1, name
+    assert all(c[0] > c[1] for c in counts), name
+    # at least 0.3 of the frame; the view-all camera (90 degrees, the whole box in view) shows
+    # the globe on ~0.1 of the frame, so there the bound is 0.3 of the pixels that can hit
+    assert hit >= (0.3 * disc if "_viewall" in name else 0.3), name
+    assert inv_mc >= 1, name
+
+
+def _corner_dirs(c):
+    lat, lon = c["lat"].astype(np.float64), c["lon"].astype(np.float64)
+    return np.stack([np.cos(lat) * np.cos(lon), np.cos(lat) * np.sin(lon), np.sin(lat)], 1)
+
+
+def _radius32(p):
+    """|p| as toSpherical computes it: sqrtf(x*x + y*y + z*z) in float."""
+    p = np.asarray(p, np.float32)
+    return np.sqrt(np.float32(np.float32(p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]))
+
+
+def make_terrain_kats_grid(cells, rng, zero_thickness):
+    """Known answers on one convert_icon-layout grid: see make_terrain_kats."""
+    from golden_util import terrain_fh_probes
+    from helpers import on_radius
+    import hashlib
+    R = O.rlib()
+    up, dn = np.float32(np.inf), np.float32(-np.inf)
+    out = {"cells": cells.view(np.uint8).reshape(cells.size, 284)}
+    # ---- findHeight
+    fi, fh = terrain_fh_probes(cells)
+    res = np.array([R.ref_find_height(cells[i:i + 1].ctypes.data, float(h))
+                    for i, h in zip(fi, fh)], np.int32)
+    assert res.min() >= 0 and res.max() <= 31
+    out["fh_result"] = res.astype(np.int8)
+    out["fh_sha256"] = np.frombuffer(hashlib.sha256(fi.tobytes() + fh.tobytes()).digest(), np.uint8)
+    # ---- per-cell sample(): inside and just outside the triangle, at the radii that matter
+    H0 = cells["height"][:, 0]
+    top = cells["height"][np.arange(cells.size), cells["numLayers"]]
+    inverted = (cells["numLayers"] > 0) & (H0 > cells["height"][:, 1])
+    pts, idx = [], []
+    ncol = cells.size // 3
+    for c in range(0, ncol, 4):
+        for i in range(3 * c, 3 * c + 3):
+            cell = cells[i]
+            cd = _corner_dirs(cell)
+            nl = int(cell["numLayers"])
+            h = cell["height"]
+            base = [h[0], h[1], h[nl]] if nl > 0 else [h[0]]
+            radii = [r for b in base for r in (b, np.nextafter(b, up), np.nextafter(b, dn))]
+            if nl > 0 and h[0] > h[1]:  # inside the inverted first layer
+                radii.append(np.float32((np.float64(h[0]) + np.float64(h[1])) * 0.5))
+            e = 2e-2 if i % 2 else 1e-4
+            k = int(rng.integers(3))
+            w_out = np.full(3, 0.5 + e / 2)
+            w_out[k] = -e  # just beyond the edge opposite corner k
+            for w in (rng.dirichlet([2, 2, 2]), w_out):
+                for r in radii:
+                    pts.append(on_radius(w @ cd, r))
+                    idx.append(i)
+    pts, idx = np.array(pts, np.float32), np.array(idx, np.int32)
+    hit, val = np.zeros(len(pts), np.uint8), np.zeros(len(pts), np.float32)
+    for k, (p, i) in enumerate(zip(pts, idx)):
+        v = C.c_float(0)
+        hit[k] = R.ref_sample(cells[i:i + 1].ctypes.data, p.ctypes.data, C.byref(v))
+        val[k] = v.value if hit[k] else 0.0
+    out.update(sample_points=pts, sample_cell=idx, sample_hit=hit, sample_value=val)
+    # ---- scene-level sampleVolume
+    sbl, sbu = float(H0.min()), float(top.max())
+    sp = list(pts[::3])
+    land = [c for c in range(ncol) if inverted[3 * c]]
+    assert len(land) > ncol // 4
+    for c in rng.choice(ncol, 100, replace=False):  # shared edges and a corner
+        cell = cells[3 * c]
+        cd = _corner_dirs(cell)
+        hs = float(H0[3 * c]) - sbl  # this column's surface above the lowest one
+        for a, b in ((0, 1), (1, 2), (2, 0)):
+            for r in (H0[3 * c], np.float32(sbl + 0.5 * hs + 1.0), top[3 * c + 2]):
+                sp.append(on_radius(cd[a] + cd[b], r))
+        sp.append(on_radius(cd[0], np.nextafter(H0[3 * c], up)))
+    for c in rng.choice(land, 260):  # the void under a land column, and inside its first record
+        cd = _corner_dirs(cells[3 * c])
+        w = rng.dirichlet([3, 3, 3])
+        sp.append(on_radius(w @ cd, np.float32(rng.uniform(sbl, float(H0[3 * c])))))
+        w = rng.dirichlet([3, 3, 3])
+        sp.append(on_radius(w @ cd, np.float32(rng.uniform(float(H0[3 * c]), float(top[3 * c])))))
+    for c in rng.choice(land, 80):  # the void over a land column's top
+        cd = _corner_dirs(cells[3 * c])
+        sp.append(on_radius(rng.dirichlet([3, 3, 3]) @ cd,
+                            np.float32(rng.uniform(float(top[3 * c + 2]) + 1.0, sbu))))
+    for c in rng.choice(ncol, 120):  # above the top of everything, below the bottom
+        cd = _corner_dirs(cells[3 * c])
+        off = rng.uniform(1.0, 500.0)
+        sp.append(((rng.dirichlet([3, 3, 3]) @ cd) * (sbu + off if c % 3 else sbl - off)).astype(np.float32))
+    if zero_thickness:  # a zero-thickness record accepts every direction at its one radius
+        for c in rng.choice(ncol, 60, replace=False):
+            i = 3 * c + 2
+            assert cells["numLayers"][i] == 0
+            cd = _corner_dirs(cells[i])
+            for r in (H0[i], np.nextafter(H0[i], up), np.nextafter(H0[i], dn)):
+                sp.append(on_radius(cd.sum(0), r))
+            sp.append(on_radius(rng.normal(size=3), H0[i]))
+    d = rng.normal(size=(300, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    sp += list((d * rng.uniform(sbl - 50, sbu + 50, (300, 1))).astype(np.float32))
+    sp = np.array(sp, np.float32)
+    found, value, index = O.ref_sample_volume(cells, sp)
+    out.update(scene_points=sp, scene_found=found.astype(np.uint8), scene_value=value,
+               scene_index=index)
+    rad = np.array([_radius32(p) for p in sp], np.float32)
+    stats = dict(points=len(sp), hits=int(found.sum()),
+                 voids=int(((found == 0) & (rad >= np.float32(sbl)) & (rad <= np.float32(sbu))).sum()),
+                 inverted_hits=int(inverted[index[found == 1]].sum()),
+                 zero_thickness=int(np.isin(rad, H0[cells["numLayers"] == 0]).sum()),
+                 fh_probes=len(fh), sample_probes=len(pts), sample_hits=int(hit.sum()))
+    return out, stats
+
+
+def make_terrain_kats():
+    """kats_terrain.npz: ICONCell::findHeight, sample() and the CPU sampleVolume loop
+    (ICONGrid.h:117-145, 181-208; deviceCode.cu:119-122) from the reference's own code on the
+    records of synth_grid(2, 1, 90 | 65, terrain=4000): 960 records each, stored in the file."""
+    rng = np.random.default_rng(20261019)
+    out, total = {}, {}
+    for tag, L in (("l90", 90), ("l65", 65)):
+        cells = irt.synth_grid(2, 1, L, terrain=4000.0)
+        assert cells.size == 960
+        o, st = make_terrain_kats_grid(cells, rng, zero_thickness=(L == 65))
+        print(f"kats_terrain {tag}: {st}")
+        out.update({f"{k}_{tag}": v for k, v in o.items()})
+        for k, v in st.items():
+            total[k] = total.get(k, 0) + v
+    print(f"kats_terrain: {total}")
+    # conditions on the inputs (the point recipe above is chosen so the reference meets them)
+    assert 3 * total["hits"] >= total["points"], total
+    assert total["voids"] >= 200 and total["inverted_hits"] >= 200, total
+    assert total["zero_thickness"] >= 50, total
+    np.savez_compressed(os.path.join(HERE, "kats_terrain.npz"), **out)
+
+
+def make_terrain_fixtures():
+    for name, spec in TERRAIN_FRAMES.items():
+        make_frame(name, spec, check=check_terrain_frame)
+    make_terrain_kats()
+    for name in list(TERRAIN_FRAMES) + ["kats_terrain"]:
+        n = os.path.getsize(os.path.join(HERE, name + ".npz"))
+        print(f"{name}.npz: {n} bytes")
+        assert n <= MAX_FIXTURE_BYTES, (name, n)
+
+
 if __name__ == "__main__":
     if not O.have_ref():
         sys.exit("oracle/_ref/libiconref.so missing: make -C oracle ref (needs /root/reference)")
+    if len(sys.argv) > 1 and sys.argv[1] == "terrain":
+        make_terrain_fixtures()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "grid":
         make_grid_fixtures()
         sys.exit(0)
@@ -412,3 +609,4 @@ if __name__ == "__main__":
     make_kats()
     make_grid_fixtures()
     make_wedge_fixtures()
+    make_terrain_fixtures()

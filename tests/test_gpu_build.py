@@ -22,6 +22,10 @@ def _scenes():
         "r2b02_l90": irt.synth_grid(2, 2, 90),
         "r2b03_l47_noise": irt.synth_grid(2, 3, 47, noise=0.2),
         "terrain": terrain_cells(11),                   # spheres, unsorted, inverted records
+        # the layout convert_icon writes: inverted first layers over land, voids under them;
+        # 65 levels: a zero-thickness top record per column (the sphere table)
+        "convert_icon_l90": irt.synth_grid(2, 1, 90, terrain=4000.0),
+        "convert_icon_l65": irt.synth_grid(2, 1, 65, terrain=4000.0),
         "filtered": irt.filter_cells(irt.synth_grid(2, 2, 20), (-30, 60), (-90, 45)),
         "empty": irt.synth_grid(1, 0, 4)[:0],
     }

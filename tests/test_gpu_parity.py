@@ -395,6 +395,158 @@ def test_convert_icon_terrain_bit_exact_with_and_without_miss_mode(levels):
     ctx.close()
 
 
+def _golden_context(d):
+    """A context and the LaunchParams of a golden frame fixture, fed through the C ABI."""
+    ctx = irt.Context(d["cells"], 0)
+    ctx.set_transfunc(d["lut"], tuple(float(v) for v in d["value_range"]), float(d["opacity_scale"]))
+    c = d["camera12"]
+    lp = irt.LaunchParams()
+    lp.org, lp.dir_00, lp.dir_du, lp.dir_dv = (irt.vec3(c[i:i + 3]) for i in (0, 3, 6, 9))
+    lp.ambientColor = irt.Vec3(1, 1, 1)
+    lp.ambientRadiance = 1.0
+    lp.unitDistance = float(d["unit_distance"])
+    lp.raygen = int(d["raygen"])
+    lp.accelMode = int(d.get("accel_mode", 0))
+    lp.mode = int(d.get("mode", 0))
+    return ctx, lp
+
+
+TERRAIN_FIXTURES = [n for n in __import__("golden_util").FRAME_FIXTURES if n.startswith("f8_terrain_")]
+
+
+@pytest.mark.parametrize("name", TERRAIN_FIXTURES)
+def test_terrain_golden_under_every_hole_variant(name):
+    """The convert_icon-layout frames of the reference itself (tests/golden/f8_terrain_*: voids
+    under land, inverted first layers, zero-thickness top records) under each way the raygen
+    treats holes -- miss mode with the located-mode void walk (what such a scene selects), the
+    hole-free variant forced, and miss mode alone: accum bits, fb and the per-frame counts of
+    the reference's output, not the oracle's."""
+    from golden_util import load
+    assert len(TERRAIN_FIXTURES) == 5
+    d = load(name)
+    W, H = int(d["width"]), int(d["height"])
+    ctx, lp = _golden_context(d)
+    L = irt.lib()
+    L.irt_debug_set_variant.argtypes = [C.c_void_p, C.c_int]
+    L.irt_debug_get_variant.argtypes = [C.c_void_p]
+    dv = L.irt_debug_default_variant()
+    VOIDLOC = 1073741824
+    if os.environ.get("IRT_RENDER_VARIANT"):  # a forced variant (A/B runs of the suite)
+        dv = int(os.environ["IRT_RENDER_VARIANT"]) & ~(262144 | VOIDLOC)
+    assert L.irt_debug_get_variant(ctx._h) in (dv, dv | 262144, dv | VOIDLOC)
+    if not os.environ.get("IRT_RENDER_VARIANT"):
+        assert L.irt_debug_get_variant(ctx._h) == dv | VOIDLOC
+    for v in (dv | VOIDLOC, dv, dv | 262144):
+        assert L.irt_debug_set_variant(ctx._h, v) == 0
+        fr = GpuFrame(ctx, W, H)
+        for k, aid in enumerate(d["accum_ids"]):
+            lp.accumID = int(aid)
+            st = fr.render(lp)
+            assert (st.locateCalls, st.samplesFound) == tuple(int(c) for c in d["counts"][k]), (v, k)
+            assert st.locateCalls > st.samplesFound  # the voids
+        a, f = fr.host()
+        assert_same_frame(a, f, d["accum"], d["fb"], f"{name} variant {v}")
+    ctx.close()
+
+
+def test_terrain_golden_progressive_chained():
+    """f8_terrain_r2b02_l65_progressive (the reference's frames 0, 2, 3 over zero-thickness top
+    records) through the multi-frame launches.  irt_render_sequence chains exactly the
+    fixture's accumIDs in one launch: accum bits, fb and the summed counts of the reference.
+    irt_render_accumulate chains consecutive ids only, so ids 0..3 go in one chained batch and
+    are compared with four single launches -- whose frames 0, 2, 3 must give the reference's
+    per-frame counts; the fixture's final accum itself is reached by the single launches of its
+    own ids (test_gpu_matches_reference_golden)."""
+    import torch
+    from golden_util import load
+    d = load("f8_terrain_r2b02_l65_progressive")
+    W, H = int(d["width"]), int(d["height"])
+    ids = [int(a) for a in d["accum_ids"]]
+    assert ids == [0, 2, 3]
+    ctx, lp = _golden_context(d)
+    ctx.set_chain(True)
+
+    def buffers():
+        return (torch.zeros(W * H, dtype=torch.int32, device="cuda"),
+                torch.zeros(W * H * 4, dtype=torch.float32, device="cuda"))
+
+    def host(fb, acc):
+        torch.cuda.synchronize()
+        return (acc.cpu().numpy().reshape(H, W, 4), fb.cpu().numpy().view(np.uint32).reshape(H, W))
+
+    # the fixture's own ids, chained in one launch
+    lps = []
+    for aid in ids:
+        q = irt.LaunchParams.from_buffer_copy(lp)
+        q.accumID = aid
+        lps.append(q)
+    fb, acc = buffers()
+    ctx.render_sequence(lps, W, H, fb.data_ptr(), acc.data_ptr())
+    a, f = host(fb, acc)
+    st = ctx.stats()
+    assert_same_frame(a, f, d["accum"], d["fb"], "sequence of accumIDs 0, 2, 3")
+    assert (st.locateCalls, st.samplesFound) == tuple(int(c) for c in d["counts"].sum(axis=0))
+    # ids 0..3: single launches (frames 0, 2, 3 counted like the reference's) ...
+    fb, acc = buffers()
+    total = np.zeros(2, np.int64)
+    for aid in range(4):
+        lp.accumID = aid
+        ctx.render(lp, W, H, fb.data_ptr(), acc.data_ptr())
+        torch.cuda.synchronize()
+        st = ctx.stats()
+        if aid in ids:
+            assert (st.locateCalls, st.samplesFound) == tuple(int(c) for c in d["counts"][ids.index(aid)])
+        total += (st.locateCalls, st.samplesFound)
+    a_seq, f_seq = host(fb, acc)
+    # ... and the same four frames as one chained batch
+    fb, acc = buffers()
+    lp.accumID = 0
+    ctx.render_accumulate(lp, W, H, 4, fb.data_ptr(), acc.data_ptr())
+    a_bat, f_bat = host(fb, acc)
+    st = ctx.stats()
+    assert_same_frame(a_bat, f_bat, a_seq, f_seq, "chained batch 0..3")
+    assert (st.locateCalls, st.samplesFound) == tuple(total)
+    assert ctx.chain_errors() == 0
+    ctx.close()
+
+
+@pytest.mark.parametrize("entry", ["irt_debug_locate", "irt_debug_locate_wave"])
+def test_device_locator_matches_reference_on_terrain(entry):
+    """The kernel's point location against the reference's own sampleVolume loop
+    (kats_terrain.npz) on the convert_icon layout, both device paths: found flag and value bits
+    at points on shared edges between columns of different surface height, in the voids under
+    and over land, inside inverted first layers, on zero-thickness radii and above the top."""
+    from golden_util import load_kats_terrain
+    d = load_kats_terrain()
+    L = irt.lib()
+    fn = getattr(L, entry)
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    n = hits = voids = inv = 0
+    for tag in ("l90", "l65"):
+        cells = d["cells_" + tag]
+        pts = np.ascontiguousarray(d["scene_points_" + tag])
+        want_f, want_v, want_i = (d[k + tag] for k in ("scene_found_", "scene_value_", "scene_index_"))
+        ctx = irt.Context(cells, 0)
+        found = np.zeros(len(pts), np.int32)
+        value = np.zeros(len(pts), np.float32)
+        assert fn(ctx._h, pts.ctypes.data, len(pts), found.ctypes.data, value.ctypes.data) == 0, \
+            L.irt_last_error()
+        ctx.close()
+        bad = np.nonzero(((found != 0) != (want_f != 0)) |
+                         ((want_f != 0) & (bits(value) != bits(want_v))))[0]
+        assert bad.size == 0, (tag, bad.size, pts[bad[:5]], found[bad[:5]], want_f[bad[:5]])
+        # the inputs' conditions again, on what the device returned
+        top = cells["height"][np.arange(cells.size), cells["numLayers"]]
+        p = pts.astype(np.float32)
+        r = np.sqrt(p[:, 0] * p[:, 0] + p[:, 1] * p[:, 1] + p[:, 2] * p[:, 2])
+        inverted = (cells["numLayers"] > 0) & (cells["height"][:, 0] > cells["height"][:, 1])
+        n += len(pts)
+        hits += int((found != 0).sum())
+        voids += int(((found == 0) & (r >= cells["height"][:, 0].min()) & (r <= top.max())).sum())
+        inv += int(inverted[want_i[found != 0]].sum())
+    assert 3 * hits >= n and voids >= 200 and inv >= 200, (n, hits, voids, inv)
+
+
 @pytest.mark.skipif(not os.path.exists(irt.ALL_LIB_PATH), reason="make VARIANTS=all not built")
 def test_ab_library_variants_identical():
     """test_all_render_variants_identical on the A/B library (every variant), in a child

@@ -335,6 +335,31 @@ def test_binned_locator_on_terrain_following_columns(kind):
     assert kind != "convert_icon" or n_void > 20, n_void
 
 
+@pytest.mark.parametrize("tag", ["l90", "l65"])
+def test_binned_locator_matches_reference_on_terrain(tag):
+    """The binned lists against the reference's own sampleVolume loop (kats_terrain.npz: found,
+    value bits and the winning record) on the convert_icon layout -- not the oracle's brute force,
+    which the tests above compare with: shared edges between columns of different surface
+    height, voids under and over land, inverted first layers, zero-thickness radii."""
+    from golden_util import load_kats_terrain
+    d = load_kats_terrain()
+    cells, pts = d["cells_" + tag], d["scene_points_" + tag]
+    want_f, want_v, want_i = (d[k + tag] for k in ("scene_found_", "scene_value_", "scene_index_"))
+    D = irt.DebugScene(cells)
+    inverted = (cells["numLayers"] > 0) & (cells["height"][:, 0] > cells["height"][:, 1])
+    n_hit = n_inv = 0
+    for k, p in enumerate(pts):
+        hb, vb, recb, _ = D.locate_binned(p)
+        assert bool(hb) == bool(want_f[k]), (k, p)
+        if hb:
+            assert recb == want_i[k], (k, p, recb, want_i[k])
+            assert np.float32(vb).view(np.uint32) == want_v[k].view(np.uint32), (k, p)
+            n_hit += 1
+            n_inv += bool(inverted[recb])
+    assert 3 * n_hit >= len(pts) and n_inv >= 200 and len(pts) - n_hit >= 500
+    D.close()
+
+
 # ------------------------------------------------------------------ CUBQL_MODE wedges
 def _wedge_lib():
     import ctypes as C

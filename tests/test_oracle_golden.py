@@ -6,7 +6,8 @@ import numpy as np
 import pytest
 
 import oracle as O
-from golden_util import FRAME_FIXTURES, load, oracle_scene, params
+from golden_util import (FRAME_FIXTURES, load, load_kats_terrain, oracle_scene, params,
+                         terrain_fh_probes)
 from helpers import bits
 
 
@@ -84,6 +85,66 @@ def test_kat_sample_and_find_height(kats):
         L.oracle_get_bounds(cells[i:i + 1].ctypes.data, C.byref(b))
         got = [b.lower.x, b.lower.y, b.lower.z, b.upper.x, b.upper.y, b.upper.z]
         assert np.array_equal(bits(got), bits(kats["get_bounds"][i]))
+
+
+@pytest.fixture(scope="module")
+def kats_terrain():
+    return load_kats_terrain()
+
+
+@pytest.mark.parametrize("tag", ["l90", "l65"])
+def test_kat_terrain_find_height_and_sample(kats_terrain, tag):
+    """findHeight and sample() on the records convert_icon writes (kats_terrain.npz, from the
+    reference's own ICONGrid.h): the binary search over height[1..] of records whose first
+    layer is inverted (height[0] > height[1]) at every height, one metre outside the record,
+    inside the inverted layer and the float neighbours of each; sample() inside and just outside
+    the triangle at height[0], height[1], height[numLayers] and their neighbours, inside the
+    inverted layer (rejected on height[0]), and on zero-thickness records (l65: accepted at
+    height[0] exactly, whatever the direction).  Index, hit and value bits."""
+    import hashlib
+    d = kats_terrain
+    L = O.olib()
+    cells = d["cells_" + tag]
+    fi, fh = terrain_fh_probes(cells)
+    assert hashlib.sha256(fi.tobytes() + fh.tobytes()).digest() == d["fh_sha256_" + tag].tobytes()
+    want = d["fh_result_" + tag]
+    assert len(want) == len(fh) > 60000
+    got = np.array([L.oracle_find_height(cells[i:i + 1].ctypes.data, float(h))
+                    for i, h in zip(fi, fh)], np.int32)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, (bad.size, fi[bad[:5]], fh[bad[:5]], got[bad[:5]], want[bad[:5]])
+    inverted = (cells["numLayers"] > 0) & (cells["height"][:, 0] > cells["height"][:, 1])
+    assert inverted[fi].sum() > 10000
+    hits = 0
+    for p, i, hit, val in zip(d["sample_points_" + tag], d["sample_cell_" + tag],
+                              d["sample_hit_" + tag], d["sample_value_" + tag]):
+        v = C.c_float(0)
+        h = L.oracle_sample(cells[i:i + 1].ctypes.data, O.v3(p), C.byref(v))
+        assert h == hit, (p, i)
+        if hit:
+            hits += 1
+            assert bits([v.value])[0] == bits([val])[0], (p, i)
+    assert hits > 1000
+    if tag == "l65":
+        zt = cells["numLayers"][d["sample_cell_" + tag]] == 0
+        assert (d["sample_hit_" + tag][zt] == 1).sum() >= 50  # zero-thickness records accepting
+
+
+@pytest.mark.parametrize("locator", [0, 1, 2], ids=["literal", "scan", "dirgrid"])
+@pytest.mark.parametrize("tag", ["l90", "l65"])
+def test_kat_terrain_sample_volume(kats_terrain, tag, locator):
+    """Scene-level point location on the convert_icon layout against the reference's own
+    sampleVolume loop (lowest record index wins): the oracle's literal scan, its scan over
+    precomputed planes and its direction-voxel locator, found flag and value bits, at points
+    on shared edges between columns of different surface height, in the voids under and over
+    land columns, inside inverted first layers, on zero-thickness radii and above the top."""
+    d = kats_terrain
+    cells, pts = d["cells_" + tag], d["scene_points_" + tag]
+    found, value = O.sample_volume(cells, pts, fast=locator)
+    want_f, want_v = d["scene_found_" + tag], d["scene_value_" + tag]
+    bad = np.nonzero((found != want_f) | ((want_f == 1) & (bits(value) != bits(want_v))))[0]
+    assert bad.size == 0, (bad.size, pts[bad[:5]], found[bad[:5]], want_f[bad[:5]])
+    assert 3 * int(want_f.sum()) >= len(pts) > 3000 and int((want_f == 0).sum()) > 500
 
 
 def test_kat_rays_and_sdda(kats):
@@ -253,8 +314,11 @@ def test_reference_pixel_list_render_matches_oracle():
 
 
 def test_dirgrid_locator_matches_scan_on_degenerate_scenes():
-    """The CPU baseline's locator (oracle fast=2) == the reference's scan on scenes with
-    cone-mode triangles, terrain, unsorted/zero-thickness/inverted records."""
+    """The CPU baseline's locator (oracle fast=2) == the oracle's scan on scenes with
+    cone-mode triangles, terrain, unsorted/zero-thickness/inverted records.  The oracle against
+    itself: the convert_icon terrain layout is pinned to the reference by the f8_terrain_*
+    frames (test_frame_fixture, both locators) and kats_terrain.npz
+    (test_kat_terrain_sample_volume)."""
     import irt
     from helpers import FRAMING, terrain_cells
     for cells, W in ((irt.synth_grid(1, 0, 4), 64), (terrain_cells(11), 80),
