@@ -83,6 +83,14 @@ struct irt_context {
   float *d_srgb = nullptr;
   float *d_valueRanges = nullptr;
   float *d_maxOp = nullptr;
+  // Value updates (irt_update_values*): the records' clamped shell rectangles as k_shell_build
+  // found them (8 B per record; the records themselves are gone after creation), the data
+  // range's reduction words (k_shell_rebuild), the marker a device-pointer update leaves on its
+  // caller's stream, and whether an update awaits irt_update_values_end
+  ushort4 *d_rects = nullptr;
+  unsigned long long *d_updStat = nullptr;
+  hipEvent_t evUpd = nullptr;
+  bool updPending = false;
   // GRID_ACCEL_MODE's 256^3 grid, built on first use (ensure_grid): 201 MB and ~0.16 s at C5
   // that a sphere-mode run never needs
   bool gridBuilt = false;
@@ -259,7 +267,7 @@ void free_all(irt_context *c) {
   void *ptrs[] = {c->d_binHdr, c->d_fat, c->slot.slots, c->d_blocks, c->d_sphR, c->d_sphOff, c->d_sphRec,
                   c->d_sphBits, c->d_samples, c->d_maxOp, c->d_gridVR, c->d_gridMaxOp, c->d_gridBits, c->d_wOff, c->d_wRec, c->d_wBox, c->d_wTrig, c->d_schedOrder, c->d_schedCost, c->d_srgb, c->d_valueRanges,
                   c->d_lut, c->d_counters, c->d_counterBuckets, c->d_meta, c->d_queue, c->d_chainFlag,
-                  c->d_frameCams, c->d_tfStat};
+                  c->d_frameCams, c->d_tfStat, c->d_rects, c->d_updStat};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->d_cells) (void)hipFree(c->d_cells);
@@ -275,6 +283,7 @@ void free_all(irt_context *c) {
     if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]);
     if (c->evDone[i]) (void)hipEventDestroy(c->evDone[i]);
   }
+  if (c->evUpd) (void)hipEventDestroy(c->evUpd);
   for (auto &t : c->tileTables) (void)hipFree(t.dev);
   c->tileTables.clear();
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -524,6 +533,12 @@ int sched_prepare(irt_context *c, int numBlocks, int W, int H, int packed, int t
   return IRT_OK;
 }
 
+// between the first irt_update_values* and irt_update_values_end the accelerators are stale
+int update_pending(const char *what) {
+  set_error("%s: a value update is pending (irt_update_values_end commits it)", what);
+  return IRT_E_INVALID;
+}
+
 // buildICONGrid (hostCode.cu:668-682: initGrid + buildGrid_ICON over volbounds) on first
 // use of GRID_ACCEL_MODE (a render with IRT_ACCEL_GRID, irt_get_grid), from the scene's
 // blocks, meta words and corner trig, then the grid's majorants for the current transfer
@@ -565,6 +580,7 @@ int render_impl(irt_context *c, const irt_launch_params *lp, int W, int H, int p
     set_error("irt_render: bad argument");
     return IRT_E_INVALID;
   }
+  if (c->updPending) return update_pending("irt_render");
   if (!c->tfSet) {
     set_error("irt_render: no transfer function set (irt_set_transfunc)");
     return IRT_E_INVALID;
@@ -1270,13 +1286,17 @@ int irt_create_end(irt_context *c) {
 
   // ShellAccel{vec3i(1,1024,1024), sphericalBounds} + initGrid + buildShell_ICON
   // (hostCode.cu:652-666), majorants zero until a transfer function arrives
+  // (+ each record's shell rectangle and the reduction words, for irt_update_values_end)
   if ((rc = dalloc(c, &c->d_valueRanges, 2 * c->numMCs))) return rc;
+  if ((rc = dalloc(c, &c->d_rects, numCells)) || (rc = dalloc(c, &c->d_updStat, 3))) return rc;
+  IRT_HIP(hipEventCreateWithFlags(&c->evUpd, hipEventDisableTiming));
   launch_shell_init(c->d_valueRanges, c->numMCs, c->stream);
   if (numCells) {
     const irt_box3f &sb = c->info.sphericalBounds;
     launch_shell_build(c->d_cells, numCells, make_int3(dims[0], dims[1], dims[2]),
                        make_float3(sb.lower.x, sb.lower.y, sb.lower.z),
-                       make_float3(sb.upper.x, sb.upper.y, sb.upper.z), c->d_valueRanges, c->stream);
+                       make_float3(sb.upper.x, sb.upper.y, sb.upper.z), c->d_valueRanges, c->d_rects,
+                       c->stream);
   }
   prewarm_render(c->variant, c->stream);
   IRT_HIP(hipGetLastError());
@@ -1431,6 +1451,38 @@ void irt_destroy(irt_context *c) {
   delete c;
 }
 
+namespace {
+// A sparse transfer function (many samples per acceptance) on a scene whose table is not used by
+// every launch starts its launches' scans from the slot table, built on the first such TF
+// (irt_context::slotSparse).  Decided from the shell's ranges and majorants for the current
+// transfer function: whenever either changes (irt_set_transfunc, irt_update_values_end).
+int sparse_tf_decision(irt_context *c) {
+  c->slotSparse = false;
+  if (!c->slotAlways && (c->slot.slots || (c->slotLazy && !c->slotTried)) && c->numMCs > 0) {
+    if (!c->d_tfStat) {  // once per context (a hipFree per TF change would synchronise the device)
+      int rc = dalloc(c, &c->d_tfStat, 2);
+      if (rc) return rc;
+    }
+    double h[2] = {0.0, 0.0};
+    IRT_HIP(hipMemsetAsync(c->d_tfStat, 0, 2 * sizeof(double), c->stream));
+    launch_accept_stat(c->d_valueRanges, c->d_maxOp, c->numMCs, c->d_lut, c->lutSize, c->tfLo, c->tfHi,
+                       c->d_tfStat, c->stream);
+    IRT_HIP(hipGetLastError());
+    IRT_HIP(hipMemcpyAsync(h, c->d_tfStat, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    IRT_HIP(hipStreamSynchronize(c->stream));
+    c->tfSamples = h[1] > 0.0 ? h[0] / h[1] : 0.0;
+    if (c->tfSamples >= kSparseTfSamples) {
+      if (!c->slot.slots && !c->slotTried) {
+        int rc = build_slot_table(c, false);
+        if (rc) return rc;
+      }
+      c->slotSparse = c->slot.slots != nullptr;
+    }
+  }
+  return IRT_OK;
+}
+}  // namespace
+
 int irt_get_volume_info(const irt_context *c, irt_volume_info *info) {
   if (!c || !info) {
     set_error("irt_get_volume_info: null argument");
@@ -1446,6 +1498,7 @@ int irt_set_transfunc(irt_context *c, const irt_vec4f *lut, int size, irt_box1f 
     set_error("irt_set_transfunc: bad argument");
     return IRT_E_INVALID;
   }
+  if (c->updPending) return update_pending("irt_set_transfunc");
   IRT_HIP(hipSetDevice(c->device));
   // frames still in flight on the caller's stream read the LUT and the majorants: the
   // update is serialized after them, as the reference's TF handler is after its launches
@@ -1479,33 +1532,135 @@ int irt_set_transfunc(irt_context *c, const irt_vec4f *lut, int size, irt_box1f 
     launch_grid_bits(c->d_gridMaxOp, c->d_gridBits, c->stream);
   }
   IRT_HIP(hipGetLastError());
-  // a sparse transfer function (many samples per acceptance) on a scene whose table is not used
-  // by every launch: the slot table, built on the first such TF (irt_context::slotSparse)
-  c->slotSparse = false;
-  if (!c->slotAlways && (c->slot.slots || (c->slotLazy && !c->slotTried)) && c->numMCs > 0) {
-    if (!c->d_tfStat) {  // once per context (a hipFree per TF change would synchronise the device)
-      int rc = dalloc(c, &c->d_tfStat, 2);
-      if (rc) return rc;
-    }
-    double h[2] = {0.0, 0.0};
-    IRT_HIP(hipMemsetAsync(c->d_tfStat, 0, 2 * sizeof(double), c->stream));
-    launch_accept_stat(c->d_valueRanges, c->d_maxOp, c->numMCs, c->d_lut, size, valueRange.lower,
-                       valueRange.upper, c->d_tfStat, c->stream);
-    IRT_HIP(hipGetLastError());
-    IRT_HIP(hipMemcpyAsync(h, c->d_tfStat, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    IRT_HIP(hipStreamSynchronize(c->stream));
-    c->tfSamples = h[1] > 0.0 ? h[0] / h[1] : 0.0;
-    if (c->tfSamples >= kSparseTfSamples) {
-      if (!c->slot.slots && !c->slotTried) {
-        int rc = build_slot_table(c, false);
-        if (rc) return rc;
-      }
-      c->slotSparse = c->slot.slots != nullptr;
-    }
-  }
+  if (int rc = sparse_tf_decision(c)) return rc;
   IRT_HIP(hipStreamSynchronize(c->stream));
   c->tfSet = true;
   c->info.deviceBytes = c->bytes;
+  return IRT_OK;
+}
+
+namespace {
+// irt_update_values*: the argument checks, and the wait that orders the update after every
+// launch of the context already issued (launches run in call order, so the last one's end is
+// everyone's), as irt_set_transfunc's
+int update_begin(irt_context *c, size_t first, size_t n, const void *values, const char *what) {
+  if (!c || c->building || (n && !values) || !update_range_ok(first, n, c ? c->n : 0)) {
+    set_error("%s: null context or values, a context still being created, or records [%zu, %zu + %zu) "
+              "outside the context's %zu", what, first, first, n, c ? (size_t)c->n : (size_t)0);
+    return IRT_E_INVALID;
+  }
+  IRT_HIP(hipSetDevice(c->device));
+  if (c->launches > 0) {
+    const int last = (int)((c->launches - 1) % irt_context::kSlots);
+    if (c->pending[last]) IRT_HIP(wait_slot(c, last));
+  }
+  return IRT_OK;
+}
+// records per staged chunk of a host-pointer update (128 MiB of HBM while the call runs)
+constexpr size_t kUpdateChunk = size_t(1) << 20;
+}  // namespace
+
+int irt_update_values(irt_context *c, size_t first, size_t n, const float *values) {
+  int rc = update_begin(c, first, n, values, "irt_update_values");
+  if (rc) return rc;
+  c->updPending = true;
+  if (n == 0) return IRT_OK;
+  float *stage = nullptr;
+  const size_t cap = std::min(n, kUpdateChunk);
+  IRT_HIP(hipMallocAsync((void **)&stage, cap * 32 * sizeof(float), c->stream));
+  hipError_t e = hipSuccess;
+  for (size_t at = 0; at < n && e == hipSuccess; at += cap) {
+    const size_t m = std::min(cap, n - at);
+    // stream order keeps a chunk's copy behind the previous chunk's scatter
+    e = hipMemcpyAsync(stage, values + at * 32, m * 32 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) break;
+    launch_value_scatter(stage, first + at, m, c->d_blocks, c->stream);
+    e = hipGetLastError();
+  }
+  (void)hipFreeAsync(stage, c->stream);
+  // the caller's array is free again on return, whatever the runtime does with pageable memory
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    set_error("irt_update_values: %s", hipGetErrorString(e));
+    return IRT_E_HIP;
+  }
+  return IRT_OK;
+}
+
+int irt_update_values_device(irt_context *c, size_t first, size_t n, const float *d_values, void *stream) {
+  int rc = update_begin(c, first, n, d_values, "irt_update_values_device");
+  if (rc) return rc;
+  c->updPending = true;
+  if (n == 0) return IRT_OK;
+  hipStream_t s = (hipStream_t)stream;
+  // behind the previous device-pointer update, whatever its stream (a marker never recorded
+  // holds nothing up): updates apply in call order
+  IRT_HIP(hipStreamWaitEvent(s, c->evUpd, 0));
+  launch_value_scatter(d_values, first, n, c->d_blocks, s);
+  IRT_HIP(hipGetLastError());
+  // the commit (and every other update) runs on the context's stream: behind this scatter
+  IRT_HIP(hipEventRecord(c->evUpd, s));
+  IRT_HIP(hipStreamWaitEvent(c->stream, c->evUpd, 0));
+  return IRT_OK;
+}
+
+int irt_update_values_end(irt_context *c) {
+  if (!c || c->building) {
+    set_error("irt_update_values_end: null context, or a context still being created");
+    return IRT_E_INVALID;
+  }
+  if (!c->updPending) return IRT_OK;
+  IRT_HIP(hipSetDevice(c->device));
+  // initGrid + buildShell_ICON again (hostCode.cu:652-666), from the blocks; the data range with it
+  // (the previous commit's pass ended with its stream synchronised: the words are idle)
+  const unsigned long long init[3] = {float_key(INFINITY), float_key(-INFINITY), 0ull};
+  IRT_HIP(hipMemcpy(c->d_updStat, init, sizeof(init), hipMemcpyHostToDevice));
+  launch_shell_init(c->d_valueRanges, c->numMCs, c->stream);
+  launch_shell_rebuild(c->d_blocks, c->d_meta, c->d_rects, c->n,
+                       make_int3(c->info.shellDims[0], c->info.shellDims[1], c->info.shellDims[2]),
+                       c->d_valueRanges, c->d_updStat, c->stream);
+  IRT_HIP(hipGetLastError());
+  // the majorants for the current transfer function (zero until one is set)
+  if (c->tfSet)
+    launch_max_opacities(c->d_valueRanges, c->numMCs, c->d_lut, c->lutSize, c->tfLo, c->tfHi, c->d_maxOp,
+                         c->stream);
+  if (c->gridBuilt) {  // GRID_ACCEL_MODE's grid, if it exists: as ensure_grid built it
+    const size_t gridMCs = (size_t)kGridDim * kGridDim * kGridDim;
+    launch_shell_init(c->d_gridVR, gridMCs, c->stream);
+    if (c->n) {
+      const irt_box3f &vb = c->info.bounds;
+      launch_grid_build(c->d_blocks, c->d_meta, c->d_trig, c->n, make_float3(vb.lower.x, vb.lower.y, vb.lower.z),
+                        make_float3(vb.upper.x, vb.upper.y, vb.upper.z), c->d_gridVR, c->stream);
+    }
+    if (c->tfSet) {
+      launch_max_opacities(c->d_gridVR, gridMCs, c->d_lut, c->lutSize, c->tfLo, c->tfHi, c->d_gridMaxOp,
+                           c->stream);
+      launch_grid_bits(c->d_gridMaxOp, c->d_gridBits, c->stream);
+    }
+  }
+  IRT_HIP(hipGetLastError());
+  if (c->tfSet) {
+    if (int rc = sparse_tf_decision(c)) return rc;
+  }
+  unsigned long long st[3];
+  IRT_HIP(hipMemcpyAsync(st, c->d_updStat, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+  IRT_HIP(hipStreamSynchronize(c->stream));
+  // irt_compute_volume_info's fold of fminf/fmaxf over value[0:numLayers) in record order: the
+  // least and greatest value; where that is a zero, the fold (ties to the later argument) ends
+  // on the sign of the last zero in record order
+  auto unkey = [](unsigned long long k) {
+    const uint32_t u = (uint32_t)k;
+    return u2f((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+  };
+  float lo = unkey(st[0]), hi = unkey(st[1]);
+  if (st[2]) {
+    const float z = ((st[2] - 1ull) & 1ull) ? -0.f : 0.f;
+    if (lo == 0.f) lo = z;
+    if (hi == 0.f) hi = z;
+  }
+  c->info.dataRange = {lo, hi};
+  c->info.deviceBytes = c->bytes;
+  c->updPending = false;
   return IRT_OK;
 }
 
@@ -1709,6 +1864,7 @@ int irt_get_grid(const irt_context *c, float *valueRanges, float *maxOpacities) 
     set_error("irt_get_grid: null context");
     return IRT_E_INVALID;
   }
+  if (c->updPending) return update_pending("irt_get_grid");
   IRT_HIP(hipSetDevice(c->device));
   // the grid is a cache built on first use: building it changes no observable state
   int rc = ensure_grid(const_cast<irt_context *>(c));
@@ -1727,6 +1883,7 @@ int irt_get_shell(const irt_context *c, float *valueRanges, float *maxOpacities)
     set_error("irt_get_shell: null context");
     return IRT_E_INVALID;
   }
+  if (c->updPending) return update_pending("irt_get_shell");
   IRT_HIP(hipSetDevice(c->device));
   IRT_HIP(hipStreamSynchronize(c->stream));
   if (valueRanges)

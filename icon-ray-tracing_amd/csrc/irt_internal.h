@@ -108,6 +108,12 @@ bool triangle_locate_host(const WedgeScene &W, const irt_icon_cell *cells, float
 
 int default_threads();
 
+// irt_update_values*: records [first, first + n) lie inside a context of numCells records
+// (first + n without wrapping)
+inline bool update_range_ok(size_t first, size_t n, size_t numCells) {
+  return first <= numCells && n <= numCells - first;
+}
+
 // Synthetic RnBk grid generator (host/irt_synth.cpp): open once, fill any record range.
 int synth_open(int rootN, int bisections, int levels, float topHeight, float noise, uint32_t seed,
                float terrainHeight,

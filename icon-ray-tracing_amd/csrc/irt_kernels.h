@@ -201,8 +201,19 @@ void prewarm_render(int variant, hipStream_t s);
 void launch_debug_locate(const RenderArgs &A, const float *xyz, int n, int *found, float *value,
                          hipStream_t s, bool wave);
 void launch_shell_init(float *valueRanges, size_t numMCs, hipStream_t s);
+// rects (null: not kept): per record its clamped shell rectangle {ylo, yhi, zlo, zhi}, ylo > yhi
+// for a record that rasterises nothing -- what launch_shell_rebuild needs of the records
 void launch_shell_build(const irt_icon_cell *cells, size_t n, int3 dims, float3 lo, float3 hi,
-                        float *valueRanges, hipStream_t s);
+                        float *valueRanges, ushort4 *rects, hipStream_t s);
+// irt_update_values*: values[k * 32 + j] becomes value[j] of record first + k in its block (the
+// value halves only); d_values: device memory, 128 B per record
+void launch_value_scatter(const float *d_values, size_t first, size_t n, float4 *blocks, hipStream_t s);
+// irt_update_values_end: the shell's value ranges (initialised by launch_shell_init) from the
+// blocks, meta words and stored rectangles, as launch_shell_build makes them from the records;
+// stat[0..2] (preset to float_key(+inf), float_key(-inf), 0): the data range's least and greatest
+// float_key and the last zero (k_shell_rebuild, irt_kernels.hip)
+void launch_shell_rebuild(const float4 *blocks, const uint32_t *meta, const ushort4 *rects, size_t n,
+                          int3 dims, float *valueRanges, unsigned long long *stat, hipStream_t s);
 void launch_grid_build(const float4 *blocks, const uint32_t *meta, const float4 *trig, size_t n,
                        float3 lo, float3 hi, float *valueRanges, hipStream_t s);
 void launch_grid_bits(const float *maxOp, uint32_t *bits, hipStream_t s);

@@ -62,10 +62,82 @@ __device__ __forceinline__ void shell_write(const ShellRect &q, long k, int3 dim
   atomic_max_f(vr + 1, q.hi);
 }
 
+// A record's (lo, hi) over its layers with the CAS loops' "store only if strictly
+// smaller/larger" semantics (NaN never stores; +-inf and IRT_FLT_MAX behave as in the
+// reference), for nl >= 1.  R gives height(j) and value(j): the `.ic` record staged at creation
+// (k_shell_build), the record's height/value block afterwards (k_shell_rebuild).
+template <class R>
+__device__ __forceinline__ int find_height_rec(const R &c, int nl, float hpos) {  // ICONGrid.h:117-145
+  int first = 0, count = nl;
+  while (count > 0) {
+    const int step = count / 2, it = first + step;
+    if (!(hpos <= c.height(it + 1))) {
+      first = it + 1;
+      count -= step + 1;
+    } else {
+      count = step;
+    }
+  }
+  return first;
+}
+template <class R>
+__device__ __forceinline__ void shell_record_range(const R &c, int nl, float &lo, float &hi) {
+  lo = IRT_FLT_MAX, hi = -IRT_FLT_MAX;
+  bool sorted = true;
+  for (int j = 1; j <= nl; ++j)
+    if (!(float_key(c.height(j - 1)) <= float_key(c.height(j)))) sorted = false;
+  if (sorted) {
+    int f = 0;  // findHeight(h[i])
+    float hp = c.height(0);
+    for (int i = 0; i < nl; ++i) {
+      const float v0 = c.value(f);  // getValue(h[i])
+      const float h1 = c.height(i + 1);
+      f = h1 == hp ? f : i;  // findHeight(h[i+1])
+      hp = h1;
+      const float v1 = c.value(f);  // getValue(h[i+1])
+      if (v0 < lo) lo = v0;
+      if (v1 > hi) hi = v1;
+    }
+  } else {
+    for (int i = 0; i < nl; ++i) {
+      const float v0 = c.value(find_height_rec(c, nl, c.height(i)));      // getValue(h[i])
+      const float v1 = c.value(find_height_rec(c, nl, c.height(i + 1)));  // getValue(h[i+1])
+      if (v0 < lo) lo = v0;
+      if (v1 > hi) hi = v1;
+    }
+  }
+}
+
+// A record's rectangle into the shell: in this lane, or (wider than kShellSmall macrocells) on
+// the list k_shell_rects takes.
+__device__ __forceinline__ void shell_emit(const ShellRect &q, int3 dims, float *valueRanges, ShellRect *wide,
+                                           unsigned long long *numWide, size_t wideCap) {
+  const long total = (long)q.nx * q.ny * q.nz;
+  if (total > kShellSmall && numWide) {
+    const unsigned long long k = atomicAdd(numWide, 1ull);
+    if (k < wideCap) {
+      wide[k] = q;
+      return;
+    }  // list full: this lane does it
+  }
+  for (long k = 0; k < total; ++k) shell_write(q, k, dims, valueRanges);
+}
+
+// A record's clamped rectangle as creation keeps it for irt_update_values_end (8 B per record;
+// dims.x = 1 and the shell is 1024 x 1024, so x is not stored): {ylo, yhi, zlo, zhi}, or
+// rect_none() (ylo > yhi) for a record that rasterises nothing.
+__device__ __forceinline__ ushort4 rect_none() { return make_ushort4(1, 0, 1, 0); }
+
+struct CellRec {  // the `.ic` record
+  const irt_icon_cell &c;
+  __device__ float height(int j) const { return c.height[j]; }
+  __device__ float value(int j) const { return c.value[j]; }
+};
+
 __global__ void __launch_bounds__(256) k_shell_build(const irt_icon_cell *cells, size_t n, int3 dims,
                                                      float3 sbLo, float3 sbHi, float *valueRanges,
                                                      ShellRect *wide, unsigned long long *numWide,
-                                                     size_t wideCap) {
+                                                     size_t wideCap, ushort4 *rects) {
   // 256 records (72,704 B, 16-B aligned) staged through LDS with coalesced 16-B loads: a
   // lane reading its own 284-B record straight from HBM would touch a different line with
   // every load instruction of the wave
@@ -80,35 +152,12 @@ __global__ void __launch_bounds__(256) k_shell_build(const irt_icon_cell *cells,
     for (int v = threadIdx.x; v < nv; v += blockDim.x) s_rec[v] = src[v];
     __syncthreads();
     if (threadIdx.x >= nb) continue;
+    if (rects) rects[b0 + threadIdx.x] = rect_none();  // until the record proves otherwise
     const irt_icon_cell &c = reinterpret_cast<const irt_icon_cell *>(s_rec)[threadIdx.x];
     const int nl = c.numLayers;
     if (nl <= 0) continue;
-    // min/max over the layers with the CAS loops' "store only if strictly smaller/larger"
-    // semantics (NaN never stores; +-inf and IRT_FLT_MAX behave as in the reference)
-    float lo = IRT_FLT_MAX, hi = -IRT_FLT_MAX;
-    bool sorted = true;
-    for (int j = 1; j <= nl; ++j)
-      if (!(float_key(c.height[j - 1]) <= float_key(c.height[j]))) sorted = false;
-    if (sorted) {
-      int f = 0;  // findHeight(h[i])
-      float hp = c.height[0];
-      for (int i = 0; i < nl; ++i) {
-        const float v0 = c.value[f];  // getValue(h[i])
-        const float h1 = c.height[i + 1];
-        f = h1 == hp ? f : i;  // findHeight(h[i+1])
-        hp = h1;
-        const float v1 = c.value[f];  // getValue(h[i+1])
-        if (v0 < lo) lo = v0;
-        if (v1 > hi) hi = v1;
-      }
-    } else {
-      for (int i = 0; i < nl; ++i) {
-        const float v0 = c.value[find_height(c.height, nl, c.height[i])];      // getValue(h[i])
-        const float v1 = c.value[find_height(c.height, nl, c.height[i + 1])];  // getValue(h[i+1])
-        if (v0 < lo) lo = v0;
-        if (v1 > hi) hi = v1;
-      }
-    }
+    float lo, hi;
+    shell_record_range(CellRec{c}, nl, lo, hi);
     int ylo = 0x7fffffff, yhi = (int)0x80000000u, zlo = 0x7fffffff, zhi = (int)0x80000000u;
     int xlo = 0x7fffffff, xhi = (int)0x80000000u;
     for (int k = 0; k < 3; ++k) {
@@ -125,16 +174,10 @@ __global__ void __launch_bounds__(256) k_shell_build(const irt_icon_cell *cells,
     xlo = max(xlo, 0); ylo = max(ylo, 0); zlo = max(zlo, 0);
     xhi = min(xhi, dims.x - 1); yhi = min(yhi, dims.y - 1); zhi = min(zhi, dims.z - 1);
     if (xlo > xhi || ylo > yhi || zlo > zhi) continue;
+    if (rects) rects[b0 + threadIdx.x] = make_ushort4((unsigned short)ylo, (unsigned short)yhi,
+                                                      (unsigned short)zlo, (unsigned short)zhi);
     const ShellRect q = {xlo, ylo, zlo, xhi - xlo + 1, yhi - ylo + 1, zhi - zlo + 1, lo, hi};
-    const long total = (long)q.nx * q.ny * q.nz;
-    if (total > kShellSmall && numWide) {
-      const unsigned long long k = atomicAdd(numWide, 1ull);
-      if (k < wideCap) {
-        wide[k] = q;
-        continue;
-      }  // list full: this lane does it
-    }
-    for (long k = 0; k < total; ++k) shell_write(q, k, dims, valueRanges);
+    shell_emit(q, dims, valueRanges, wide, numWide, wideCap);
   }
 }
 
@@ -146,6 +189,104 @@ __global__ void __launch_bounds__(256) k_shell_rects(const ShellRect *wide, cons
     const ShellRect q = wide[b];
     const long total = (long)q.nx * q.ny * q.nz;
     for (long k = threadIdx.x; k < total; k += blockDim.x) shell_write(q, k, dims, valueRanges);
+  }
+}
+
+// ------------------------------------------------------------------ value updates
+// irt_update_values*: records [first, first + n) get new value[0..31], 128 B per record,
+// contiguous in `values`.  Eight lanes per record: lane l of a record loads float4 l
+// (value[4l..4l+3]; a wave's loads are one contiguous 1-KiB run) and stores value float4 l of the
+// record's block, {value[4l-1], value[4l], value[4l+1], value[4l+2]} -- blk_value_pos keeps the
+// values rotated by one, value[31] in block 0's slot 8 -- with its first word from the
+// neighbouring lane's last.  The blocks' height halves are not touched.  ALIGNED: `values` is
+// 16-B aligned (a caller's device pointer need not be).
+template <bool ALIGNED>
+__global__ void __launch_bounds__(256) k_value_scatter(const float *values, size_t first, size_t n,
+                                                       float4 *blocks) {
+  const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;  // float4 t of values
+  const bool valid = t < 8 * n;  // a record's eight lanes are valid together
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (valid) {
+    if (ALIGNED) {
+      v = reinterpret_cast<const float4 *>(values)[t];
+    } else {
+      const float *p = values + 4 * t;
+      v = make_float4(p[0], p[1], p[2], p[3]);
+    }
+  }
+  const int lane = (int)(threadIdx.x & 63);
+  const float prev = __shfl(v.w, (lane & ~7) | ((lane + 7) & 7), 64);
+  if (!valid) return;
+  const int l = (int)(t & 7);
+  blocks[(first + (t >> 3)) * kBlk4 + 4 * (l >> 1) + 2 + (l & 1)] = make_float4(prev, v.x, v.y, v.z);
+}
+
+// irt_update_values_end: the shell's value ranges again (after k_shell_init) from the updated
+// blocks, the meta words (numLayers) and the rectangles k_shell_build stored -- per record the
+// same (lo, hi) into the same macrocells as at creation.  256 records' blocks staged through
+// LDS as in k_shell_build, at a stride of 65 words: lane r's word j sits in bank (r + j) % 64,
+// so neither the staging stores nor the lanes' reads of their own records conflict.
+// The same pass folds the data range, min/max of value[0:numLayers) (NaN never counts, as
+// fminf/fmaxf skip it): stat[0] = the least float_key, stat[1] = the greatest, stat[2] = 1 +
+// (((record * 32 + layer) << 1) | sign) of the last zero in record order -- the host's fold,
+// whose fminf/fmaxf return their second argument on a tie, ends on that zero's sign when the
+// minimum or maximum is zero (irt_context.hip irt_update_values_end).
+struct BlockRec {  // a record's height/value block (irt_common.h kBlk4)
+  const float *b;
+  __device__ float height(int j) const { return b[blk_height_pos(j)]; }
+  __device__ float value(int j) const { return b[blk_value_pos(j)]; }
+};
+constexpr int kRebuildRecs = 256, kRebuildStride = 4 * kBlk4 + 1;
+
+__global__ void __launch_bounds__(256) k_shell_rebuild(const float4 *blocks, const uint32_t *meta,
+                                                       const ushort4 *rects, size_t n, int3 dims,
+                                                       float *valueRanges, ShellRect *wide,
+                                                       unsigned long long *numWide, size_t wideCap,
+                                                       unsigned long long *stat) {
+  __shared__ float s_blk[kRebuildRecs * kRebuildStride];
+  float dlo = __builtin_inff(), dhi = -__builtin_inff();
+  unsigned long long zero = 0ull;
+  for (size_t b0 = (size_t)blockIdx.x * kRebuildRecs; b0 < n; b0 += (size_t)gridDim.x * kRebuildRecs) {
+    const size_t nb = n - b0 < (size_t)kRebuildRecs ? n - b0 : (size_t)kRebuildRecs;
+    const int nv = (int)nb * kBlk4;
+    const float4 *src = blocks + b0 * kBlk4;
+    __syncthreads();  // the previous batch is done with s_blk
+    for (int v = threadIdx.x; v < nv; v += blockDim.x) {
+      const float4 q = src[v];
+      float *d = s_blk + (v >> 4) * kRebuildStride + 4 * (v & 15);
+      d[0] = q.x, d[1] = q.y, d[2] = q.z, d[3] = q.w;
+    }
+    __syncthreads();
+    if (threadIdx.x >= nb) continue;
+    const size_t i = b0 + threadIdx.x;
+    const BlockRec c{s_blk + threadIdx.x * kRebuildStride};
+    const int nl = (int)(meta[i] & 31u);
+    for (int j = 0; j < nl; ++j) {
+      const float v = c.value(j);
+      if (v < dlo) dlo = v;
+      if (v > dhi) dhi = v;
+      if (v == 0.f) zero = 1ull + ((((unsigned long long)i * 32ull + (unsigned)j) << 1) | (__float_as_uint(v) >> 31));
+    }
+    const ushort4 r = rects[i];
+    if (nl <= 0 || r.x > r.y) continue;
+    float lo, hi;
+    shell_record_range(c, nl, lo, hi);
+    const ShellRect q = {0, (int)r.x, (int)r.z, 1, (int)r.y - (int)r.x + 1, (int)r.w - (int)r.z + 1, lo, hi};
+    shell_emit(q, dims, valueRanges, wide, numWide, wideCap);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const float a = __shfl_xor(dlo, off, 64), b = __shfl_xor(dhi, off, 64);
+    const unsigned long long z = __shfl_xor(zero, off, 64);
+    dlo = a < dlo ? a : dlo;
+    dhi = b > dhi ? b : dhi;
+    zero = z > zero ? z : zero;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (dlo <= dhi) {  // the wave saw a value
+      atomicMin(&stat[0], (unsigned long long)float_key(dlo));
+      atomicMax(&stat[1], (unsigned long long)float_key(dhi));
+    }
+    if (zero) atomicMax(&stat[2], zero);
   }
 }
 
@@ -408,27 +549,59 @@ void launch_shell_init(float *vr, size_t numMCs, hipStream_t s) {
   hipLaunchKernelGGL(k_shell_init, dim3((unsigned)((numMCs + 255) / 256)), dim3(256), 0, s,
                      (float2 *)vr, numMCs);
 }
+namespace {
+// the wide-rectangle list of a shell pass over n records: sized for the seam and polar
+// columns, capped (overflow stays in-lane); without scratch memory every rectangle in-lane
+struct WideList {
+  ShellRect *wide = nullptr;
+  unsigned long long *num = nullptr;
+  size_t cap = 0;
+  WideList(size_t n, hipStream_t s) {
+    cap = std::min<size_t>(n / 8 + 4096, size_t(1) << 22);
+    if (hipMallocAsync((void **)&wide, cap * sizeof(ShellRect), s) != hipSuccess ||
+        hipMallocAsync((void **)&num, sizeof(unsigned long long), s) != hipSuccess) {
+      (void)hipGetLastError();
+      if (wide) (void)hipFreeAsync(wide, s);
+      wide = nullptr, num = nullptr, cap = 0;
+      return;
+    }
+    (void)hipMemsetAsync(num, 0, sizeof(unsigned long long), s);
+  }
+  // after the pass: the listed rectangles, a workgroup each
+  void finish(int3 dims, float *vr, hipStream_t s) {
+    if (!num) return;
+    hipLaunchKernelGGL(k_shell_rects, dim3(2048), dim3(256), 0, s, wide, num, cap, dims, vr);
+    (void)hipFreeAsync(wide, s);
+    (void)hipFreeAsync(num, s);
+  }
+};
+}  // namespace
+
 void launch_shell_build(const irt_icon_cell *cells, size_t n, int3 dims, float3 lo, float3 hi,
-                        float *vr, hipStream_t s) {
+                        float *vr, ushort4 *rects, hipStream_t s) {
   if (n == 0) return;
   const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
-  // the wide-rectangle list: sized for the seam and polar columns, capped (overflow stays
-  // in-lane)
-  const size_t cap = std::min<size_t>(n / 8 + 4096, size_t(1) << 22);
-  ShellRect *wide = nullptr;
-  unsigned long long *numWide = nullptr;
-  if (hipMallocAsync((void **)&wide, cap * sizeof(ShellRect), s) != hipSuccess ||
-      hipMallocAsync((void **)&numWide, sizeof(unsigned long long), s) != hipSuccess) {
-    hipLaunchKernelGGL(k_shell_build, dim3(blocks), dim3(256), 0, s, cells, n, dims, lo, hi, vr,
-                       (ShellRect *)nullptr, (unsigned long long *)nullptr, (size_t)0);
-    return;
-  }
-  (void)hipMemsetAsync(numWide, 0, sizeof(unsigned long long), s);
-  hipLaunchKernelGGL(k_shell_build, dim3(blocks), dim3(256), 0, s, cells, n, dims, lo, hi, vr, wide,
-                     numWide, cap);
-  hipLaunchKernelGGL(k_shell_rects, dim3(2048), dim3(256), 0, s, wide, numWide, cap, dims, vr);
-  (void)hipFreeAsync(wide, s);
-  (void)hipFreeAsync(numWide, s);
+  WideList W(n, s);
+  hipLaunchKernelGGL(k_shell_build, dim3(blocks), dim3(256), 0, s, cells, n, dims, lo, hi, vr, W.wide,
+                     W.num, W.cap, rects);
+  W.finish(dims, vr, s);
+}
+void launch_value_scatter(const float *d_values, size_t first, size_t n, float4 *blocks, hipStream_t s) {
+  if (n == 0) return;
+  const unsigned grid = (unsigned)((8 * n + 255) / 256);
+  if (reinterpret_cast<uintptr_t>(d_values) % 16 == 0)
+    hipLaunchKernelGGL(k_value_scatter<true>, dim3(grid), dim3(256), 0, s, d_values, first, n, blocks);
+  else
+    hipLaunchKernelGGL(k_value_scatter<false>, dim3(grid), dim3(256), 0, s, d_values, first, n, blocks);
+}
+void launch_shell_rebuild(const float4 *blocks, const uint32_t *meta, const ushort4 *rects, size_t n,
+                          int3 dims, float *vr, unsigned long long *stat, hipStream_t s) {
+  if (n == 0) return;
+  const unsigned grid = (unsigned)std::min<size_t>((n + kRebuildRecs - 1) / kRebuildRecs, 4096);
+  WideList W(n, s);
+  hipLaunchKernelGGL(k_shell_rebuild, dim3(grid), dim3(256), 0, s, blocks, meta, rects, n, dims, vr, W.wide,
+                     W.num, W.cap, stat);
+  W.finish(dims, vr, s);
 }
 void launch_grid_build(const float4 *blocks, const uint32_t *meta, const float4 *trig, size_t n,
                        float3 lo, float3 hi, float *vr, hipStream_t s) {

@@ -147,6 +147,9 @@ def lib() -> C.CDLL:
             "irt_destroy": [P],
             "irt_get_volume_info": [P, C.POINTER(VolumeInfo)],
             "irt_set_transfunc": [P, P, I, Box1, F],
+            "irt_update_values": [P, S, S, P],
+            "irt_update_values_device": [P, S, S, P, P],
+            "irt_update_values_end": [P],
             "irt_clear_frame": [P, P, P, S, P],
             "irt_render": [P, C.POINTER(LaunchParams), I, I, P, P, P],
             "irt_render_tiles": [P, C.POINTER(LaunchParams), I, I, I, I, P, P,
@@ -468,6 +471,18 @@ def _array(fn, h, name):
     return out[:n.value]
 
 
+def check_update_values(values) -> np.ndarray:
+    """The argument check of Context.update_values: a float32 array of shape (n, 32),
+    C-contiguous -- nothing is converted or copied on the way to the library."""
+    if not isinstance(values, np.ndarray) or values.dtype != np.float32:
+        raise TypeError("update_values: values must be a float32 numpy array")
+    if values.ndim != 2 or values.shape[1] != 32:
+        raise ValueError(f"update_values: values must have shape (n, 32), not {values.shape}")
+    if not values.flags.c_contiguous:
+        raise ValueError("update_values: values must be C-contiguous")
+    return values
+
+
 # ----------------------------------------------------------------------- GPU context
 class Context:
     """One renderer context on one HIP device (irt_create ... irt_destroy).
@@ -553,6 +568,25 @@ class Context:
         lut = np.ascontiguousarray(lut, dtype=np.float32).reshape(-1, 4)
         _check(lib().irt_set_transfunc(self._h, _ptr(lut), lut.shape[0], box1(*value_range),
                                        float(opacity_scale)), "irt_set_transfunc")
+
+    def update_values(self, values: np.ndarray, first: int = 0):
+        """irt_update_values: values[k, j] becomes value[j] of record first + k (all 32 j);
+        float32, shape (n, 32), C-contiguous.  Commit with end_update()."""
+        values = check_update_values(values)
+        _check(lib().irt_update_values(self._h, int(first), values.shape[0], _ptr(values)),
+               "irt_update_values")
+
+    def update_values_device(self, ptr: int, n: int, first: int = 0, stream: int = 0):
+        """irt_update_values_device: the same from n x 32 float32 in device memory at `ptr`
+        (a torch tensor's data_ptr()), enqueued on `stream`."""
+        _check(lib().irt_update_values_device(self._h, int(first), int(n), C.c_void_p(ptr),
+                                              C.c_void_p(stream)), "irt_update_values_device")
+
+    def end_update(self):
+        """irt_update_values_end: commits the updates (shell, data range, majorants, grid);
+        self.info is read again, so info.dataRange is the new range."""
+        _check(lib().irt_update_values_end(self._h), "irt_update_values_end")
+        _check(lib().irt_get_volume_info(self._h, C.byref(self.info)), "irt_get_volume_info")
 
     def set_statistics(self, on: bool):
         """Per-launch event counts on (default) or off (irt_set_statistics); frames are

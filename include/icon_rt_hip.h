@@ -162,6 +162,44 @@ int irt_get_volume_info(const irt_context *ctx, irt_volume_info *info);
 int irt_set_transfunc(irt_context *ctx, const irt_vec4f *rgbaLUT, int size,
                       irt_box1f valueRange, float opacityScale);
 
+/* ---------------------------------------------------------------- time series
+ * The next output step of a time series: the same records with new value[] (the mesh, the
+ * heights and numLayers stay).  Only the value halves of the per-record blocks, the shell's
+ * value ranges and majorants, the GRID_ACCEL_MODE grid (if built), dataRange and the sparse
+ * transfer-function decision depend on value[]; the locator, the sphere tables and the wedge
+ * locator are kept.  No counterpart in the reference, whose viewer loads one `.ic`.
+ *
+ * New values for records [first, first + n): values[k*32 + j] replaces record first+k's
+ * value[j] for all 32 j (as irt_create stores all 32).  Host pointer; copied; returns once
+ * the copy has been issued.  Any number of calls, in any order, until irt_update_values_end;
+ * calls that overlap apply in call order.
+ *  - Ordering: an update waits for every launch of the context already issued (as
+ *    irt_set_transfunc does); irt_render* calls after irt_update_values_end, on any stream, see
+ *    the committed values.
+ *  - Between the first irt_update_values* and irt_update_values_end, every irt_render* call,
+ *    irt_get_shell, irt_get_grid and irt_set_transfunc returns IRT_E_INVALID (the accelerators
+ *    are stale); irt_last_error() names the pending update.
+ *  - first + n > numCells, a NULL pointer with n > 0, a context still being created or a NULL
+ *    context: IRT_E_INVALID, nothing written.
+ *  - The values are not validated (irt_create validates none either); NaNs behave as through
+ *    irt_create: the shell's min/max never store them, the data range skips them.
+ *  - Multi-GPU: every rank's context holds the whole scene, so every rank updates its own. */
+int irt_update_values(irt_context *ctx, size_t first, size_t n, const float *values);
+/* The same from a DEVICE pointer on the context's device, enqueued on `stream`
+ * (e.g. a torch tensor's data_ptr()); d_values must stay valid until the work on `stream`
+ * has run. */
+int irt_update_values_device(irt_context *ctx, size_t first, size_t n, const float *d_values,
+                             void *stream);
+/* Commit: rebuild what depends on the values -- the shell's valueRanges from ALL records,
+ * info.dataRange, the majorants for the current transfer function (if one is set), the
+ * 256^3 grid and its majorants/bits (if built), the sparse-TF decision (as irt_set_transfunc
+ * makes it).  After it the context is indistinguishable from one created from the same
+ * records with the new values: of irt_volume_info only dataRange changes (where the new
+ * minimum or maximum is a zero, with the sign irt_compute_volume_info's fold gives it); the
+ * transfer function's valueRange is the caller's and stays.  Waits for the rebuild.  With
+ * nothing pending: IRT_OK, nothing done. */
+int irt_update_values_end(irt_context *ctx);
+
 /* == clearFramebuffer (common/pipeline.cu:171-199): fb = make_rgba(0), accum = 0. */
 int irt_clear_frame(irt_context *ctx, uint32_t *d_fb, irt_vec4f *d_accum, size_t numPixels,
                     void *stream);
