@@ -17,8 +17,11 @@ f8_terrain_*.npz + kats_terrain.npz (`make_golden.py terrain`, which writes thes
 pin the record layout convert_icon writes for real fields -- terrain-following heights, an
 inverted first layer over land (height[0] > height[1]), zero-thickness top records (65
 levels), voids under land: five frames of the reference raygen, and findHeight / sample /
-sampleVolume known answers at the radii where that layout is unobvious.  Thirteen golden
-frames in all (f1 x 2, f2..f7, f8 x 5) come from the reference's own code.
+sampleVolume known answers at the radii where that layout is unobvious.
+f9_view_*.npz (`make_golden.py views`): four frames of the terrain scene from cameras of
+helpers.view_battery -- inside the shell, under it, south of the globe (AE) and along the horizon
+(grid).  Seventeen golden frames in all (f1 x 2, f2..f7, f8 x 5, f9 x 4) come from the reference's
+own code.
 The `.ic` inputs are synthetic grids from icon-ray-tracing_amd's generator (real DWD data
 is not available offline); they are stored verbatim, so the fixtures do not depend on it.
 """
@@ -53,12 +56,15 @@ SPARSE_LUT5 = np.array([[0.1, 0.2, 0.9, 0.05], [0.9, 0.9, 0.2, 0.02], [0.8, 0.1,
                        np.float32)
 
 
-def make_frame(name, spec, mode=0, check=None):
+def make_frame(name, spec, mode=0, check=None, accel_mode=0):
     rn, bis, L, cap, W, H, cam, ids, raygen, tf = spec[:10]
     terrain = float(spec[10]) if len(spec) > 10 else 0.0
     cells = irt.synth_grid(rn, bis, L, noise=0.1 if tf == "sparse" else 0.0, terrain=terrain)
     if cap >= 0:
         cells = cells[:cap].copy()  # --num-cells (hostCode.cu:112-113,728-730)
+    if isinstance(cam, str):  # a view of helpers.view_battery, from this scene's radii
+        from helpers import view_battery
+        cam = view_battery(cells)[cam]
     S = O.OracleScene(cells)
     # host setup restated with the reference's types (oracle/_ref)
     R = O.rlib()
@@ -101,8 +107,14 @@ def make_frame(name, spec, mode=0, check=None):
     accum = np.zeros((H, W, 4), np.float32)
     fb = np.zeros((H, W), np.uint32)
     counts = []
+    if accel_mode == 1:  # GRID_ACCEL_MODE: the reference's own 256^3 grid and majorants
+        S.build_grid()
+        R.ref_build_grid(cells.ctypes.data, cells.size, S.grid_dims.ctypes.data, vb6.ctypes.data,
+                         S.grid_vr.ctypes.data)
+        R.ref_max_opacities(S.grid_vr.ctypes.data, S.grid_vr.shape[0], lut.ctypes.data, 300,
+                            vrange[0], vrange[1], S.grid_max_op.ctypes.data)
     p = S.params((cam12[0:3], cam12[3:6], cam12[6:9], cam12[9:12]), raygen=raygen,
-                 unit_distance=unit_c, mode=mode)
+                 unit_distance=unit_c, mode=mode, accel_mode=accel_mode)
     for aid in ids:
         p.accumID = aid
         _, _, c = O.ref_render(S, p, W, H, accum=accum, fb=fb, threads=1)
@@ -114,6 +126,8 @@ def make_frame(name, spec, mode=0, check=None):
         unit_distance=np.float32(unit_c), spherical_bounds=sb6, volume_bounds=vb6,
         data_range=dr, value_ranges=vr_ref, max_opacities=maxop, accum=accum, fb=fb,
         counts=np.array(counts, np.uint64), mode=mode)
+    if accel_mode:
+        out["accel_mode"] = accel_mode
     if check is not None:
         check(name, cells, out)  # before anything is written
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
@@ -592,11 +606,33 @@ def make_terrain_fixtures():
         assert n <= MAX_FIXTURE_BYTES, (name, n)
 
 
+VIEW_FRAMES = {
+    # name: (FRAMES-style spec whose camera names a view of helpers.view_battery, accelMode)
+    "f9_view_shell_down": ((2, 1, 90, -1, 48, 40, "shell_down", (0, 2, 3), 0, "default", 4000.0), 0),
+    "f9_view_underground": ((2, 1, 90, -1, 48, 40, "underground", (0,), 0, "default", 4000.0), 0),
+    "f9_view_south_oblique_ae": ((2, 1, 90, -1, 48, 40, "south_oblique", (0,), 1, "default", 4000.0), 0),
+    "f9_view_shell_horizon_grid": ((2, 1, 90, -1, 48, 40, "shell_horizon", (0,), 0, "default", 4000.0), 1),
+}
+
+
+def make_view_fixtures():
+    largest = max(os.path.getsize(os.path.join(HERE, f)) for f in os.listdir(HERE)
+                  if f.endswith(".npz") and not f.startswith("f9_view_"))
+    for name, (spec, accel) in VIEW_FRAMES.items():
+        make_frame(name, spec, accel_mode=accel)
+        n = os.path.getsize(os.path.join(HERE, name + ".npz"))
+        print(f"{name}.npz: {n} bytes")
+        assert n <= min(largest, 1 << 20), (name, n, largest)
+
+
 if __name__ == "__main__":
     if not O.have_ref():
         sys.exit("oracle/_ref/libiconref.so missing: make -C oracle ref (needs /root/reference)")
     if len(sys.argv) > 1 and sys.argv[1] == "terrain":
         make_terrain_fixtures()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "views":
+        make_view_fixtures()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "grid":
         make_grid_fixtures()
@@ -610,3 +646,4 @@ if __name__ == "__main__":
     make_grid_fixtures()
     make_wedge_fixtures()
     make_terrain_fixtures()
+    make_view_fixtures()

@@ -77,6 +77,99 @@ def gpu_frame(cells, W, H, camera=None, accum_ids=(0,), raygen=0, lut=None, valu
     return a, f, stats, ctx
 
 
+def _unit(v):
+    v = np.asarray(v, np.float64)
+    return v / np.linalg.norm(v)
+
+
+def view_battery(cells):
+    """Cameras (vp, vi, vu, fovy) inside, under, south of and beside the globe, from the
+    scene's own radii: between them the raygen's ray setup (boxTest, the two sphere tests and
+    sdda's range selection, ShellAccel.h:87-111) takes every branch -- see range_census.
+    In the order the chained-sequence tests render them; `framing` is the control."""
+    top = float(cells["height"][np.arange(cells.size), cells["numLayers"]].max())
+    bot = float(cells["height"][:, 0].min())
+    mid = 0.5 * (bot + top)
+    u = _unit((0.3, 0.5, -0.8))  # a southern direction, off every axis
+    tang = _unit(np.cross(u, (0.0, 0.0, 1.0)))
+    e = u * mid  # inside the shell
+
+    def cam(vp, vi, vu, fovy):
+        return (tuple(float(x) for x in vp), tuple(float(x) for x in vi),
+                tuple(float(x) for x in vu), float(fovy))
+
+    z, one = (0.0, 0.0, 1.0), np.ones(3)
+    graze = u * 1.0005 * top
+    return {
+        # negative latitudes, off-axis; box misses at the frame's edge
+        "south_oblique": cam((-0.9e7, -1.1e7, -0.6e7), (0, 0, 0), z, 60),
+        # t0 < st2 with st1 < 0: the first leaf lies behind the camera, then the far range
+        "shell_down": cam(e, (0, 0, 0), tang, 90),
+        # limb and two-range rays from inside the shell, long grazing segments
+        "shell_horizon": cam(e, e + tang * 1e6, u, 90),
+        # looking up from inside the shell: the line meets the inner sphere behind the camera, so
+        # the one range is [st3 < 0, st4] (at fovy 90 no ray is flat enough for s1 && !s2: the
+        # limb rays from inside are shell_horizon's)
+        "shell_up": cam(e, 2 * e, tang, 90),
+        # under the inner sphere: the far range alone (rlo0 = st3)
+        "underground": cam(u * 0.5 * bot, u * bot + tang * 3e6, tang, 90),
+        # the origin exactly at the centre
+        "centre": cam((0, 0, 0), (1e6, 2e6, -3e6), z, 90),
+        # in the box, past the sphere (st4 < t0): no range on any pixel
+        "corner_away": cam(0.95 * top * one, 2 * top * one, z, 60),
+        # every pixel misses the box: nothing may be written
+        "away": cam((0, 0, 1.4e7), (0, 0, 2.8e7), (0, 1, 0), 60),
+        # outside, tangential
+        "graze": cam(graze, graze + tang * 1e6, u, 40),
+        "framing": FRAMING,
+    }
+
+
+VIEW_NAMES = ("south_oblique", "shell_down", "shell_horizon", "shell_up", "underground", "centre",
+              "corner_away", "away", "graze", "framing")  # view_battery's keys, in its order
+NO_RANGE, LIMB_ONLY, TWO_RANGES, FAR_ONLY = 0, 1, 2, 3
+RANGE_LABELS = ("no range", "limb only", "two ranges", "far only")
+
+
+def range_census(lp, W, H, info):
+    """Which branch of the ray setup (boxTest, deviceCode.cu:294; sdda's range selection,
+    ShellAccel.h:87-111) the ray through the middle of each pixel's jitter footprint takes,
+    restated in float64: returns (label (H, W) -- NO_RANGE, LIMB_ONLY (s1 && !s2: the outer
+    sphere's chord), TWO_RANGES (tmin < t2: [t1, t2] and [t3, t4]) or FAR_ONLY ([t3, t4]) --,
+    behind (H, W): the first range starts behind the camera -- st1 < 0 on LIMB_ONLY and
+    TWO_RANGES, st3 < 0 on FAR_ONLY (a camera in the shell looking up: the line meets the inner
+    sphere behind it) --, and inBox (H, W): boxTest passed; a ray that misses the box is
+    NO_RANGE)."""
+    f8 = lambda v: np.array(v.tolist(), np.float64)  # noqa: E731
+    org, d00, du, dv = f8(lp.org), f8(lp.dir_00), f8(lp.dir_du), f8(lp.dir_dv)
+    ys, xs = np.mgrid[0:H, 0:W]
+    # generateRay: (x + .5 + jitter) * du, jitter uniform in [0, 1)
+    d = d00 + (xs[..., None] + 1.0) * du + (ys[..., None] + 1.0) * dv
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lo = (f8(info.bounds.lower) - org) / d
+        hi = (f8(info.bounds.upper) - org) / d
+        t0 = np.maximum(0.0, np.minimum(lo, hi).max(-1))
+        t1 = np.minimum(1e10, np.maximum(lo, hi).min(-1))
+        in_box = t0 < t1
+
+        def sphere(radius):
+            b = 2.0 * (d @ org)
+            c = org @ org - radius * radius
+            disc = b * b - 4.0 * c
+            s = np.sqrt(np.maximum(disc, 0.0))
+            q = np.where(b < 0, -0.5 * (b - s), -0.5 * (b + s))
+            ta, tb = q, c / q
+            return disc >= 0, np.fmin(ta, tb), np.fmax(ta, tb)
+
+        s1, st1, st4 = sphere(float(info.sphericalBounds.upper.x))
+        s2, st2, st3 = sphere(float(info.sphericalBounds.lower.x))
+    label = np.where(s1 & ~s2, LIMB_ONLY, np.where(t0 < st2, TWO_RANGES, FAR_ONLY))
+    label = np.where(in_box & (s1 | s2) & ~(st4 < t0), label, NO_RANGE)
+    behind = (label != NO_RANGE) & (np.where(label == FAR_ONLY, st3, st1) < 0)
+    return label, behind, in_box
+
+
 def terrain_cells(seed=11, bisections=1, levels=70):
     """A synthetic scene with terrain-following record boundaries (per-column offsets, like
     ICON's HHL), a few unsorted-height records, zero-thickness records (numLayers 0, as
