@@ -987,7 +987,9 @@ int irt_create_begin(size_t numCells, int device, irt_context **out) {
     c->schedPolicy = atoi(e);
     c->schedFixed = true;
   }
-  if (hipMalloc((void **)&c->d_cells, std::max<size_t>(numCells, 1) * sizeof(irt_icon_cell)) != hipSuccess ||
+  // 16 B more than the records: k_shell_build stages them as whole float4, and 284 B records end
+  // on a 16-B boundary only for numCells % 4 == 0 (the bytes past the last record are never used)
+  if (hipMalloc((void **)&c->d_cells, std::max<size_t>(numCells, 1) * sizeof(irt_icon_cell) + 16) != hipSuccess ||
       hipMalloc((void **)&c->d_trig, std::max<size_t>(numCells, 1) * 3 * sizeof(float4)) != hipSuccess) {
     set_error("irt_create: cannot allocate %zu cells in HBM", numCells);
     return fail(IRT_E_HIP);
@@ -2169,6 +2171,7 @@ extern "C" int irt_debug_context_array(const irt_context *c, int which, void *ds
     case IRT_DEBUG_ARRAY_SPH_REC: src = c->d_sphRec; n = (size_t)c->numSphRec * 8; break;
     case IRT_DEBUG_ARRAY_SPH_BITS: src = c->d_sphBits; n = (size_t)kSphBitWords * 4; break;
     case IRT_DEBUG_ARRAY_SLOTS: src = c->slot.slots; n = c->slot.bytes; break;
+    case IRT_DEBUG_ARRAY_GRID_BITS: src = c->d_gridBits; n = c->gridBuilt ? (size_t)kGridBitWords * 4 : 0; break;
     default:
       set_error("irt_debug_context_array: unknown array %d", which);
       return IRT_E_INVALID;

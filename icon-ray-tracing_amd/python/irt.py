@@ -458,8 +458,9 @@ def setup_frame(cells: np.ndarray, width: int, height: int, camera=None,
 SCENE_ARRAYS = {"bin_hdr": 0, "fat": 1, "blocks": 2, "sph_r": 3, "sph_off": 4, "sph_rec": 5,
                 "sph_bits": 6}
 # ... and those only a context holds: the slot table (irt_common.h kSlot4; empty when the
-# scene's cells do not share their radial edges, or with IRT_SLOTS=0)
-CONTEXT_ARRAYS = {"slots": 7}
+# scene's cells do not share their radial edges, or with IRT_SLOTS=0) and GRID_ACCEL_MODE's
+# empty-space bitmap (k_grid_bits; empty until the grid is built)
+CONTEXT_ARRAYS = {"slots": 7, "grid_bits": 8}
 
 
 def _array(fn, h, name):

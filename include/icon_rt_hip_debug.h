@@ -78,8 +78,11 @@ enum {
   IRT_DEBUG_ARRAY_SPH_OFF = 4,  /* CSR offsets (u32) */
   IRT_DEBUG_ARRAY_SPH_REC = 5,  /* (record, numLayers) u32 pairs */
   IRT_DEBUG_ARRAY_SPH_BITS = 6, /* radius hash bitmap (u32) */
-  IRT_DEBUG_ARRAY_SLOTS = 7     /* the slot table (irt_common.h kSlot4), 128 B per (cell, sub-cell,
+  IRT_DEBUG_ARRAY_SLOTS = 7,    /* the slot table (irt_common.h kSlot4), 128 B per (cell, sub-cell,
                                    bin); 0 bytes when the scene has none (context only) */
+  IRT_DEBUG_ARRAY_GRID_BITS = 8 /* GRID_ACCEL_MODE's empty-space bitmap (u32; bit b: block b of 8^3
+                                   grid cells, x fastest, holds a majorant not <= 0); 0 bytes
+                                   until the grid is built (context only) */
 };
 int irt_debug_context_array(const irt_context *ctx, int which, void *dst, size_t capacity,
                             size_t *bytes);
