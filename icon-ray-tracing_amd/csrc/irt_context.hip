@@ -2122,6 +2122,52 @@ extern "C" int irt_debug_locate_wave(irt_context *c, const float *xyz, int n, in
   return debug_locate(c, xyz, n, found, value, true);
 }
 
+extern "C" int irt_debug_locate_sampler(irt_context *c, int mode, const float *xyz, int n, int *found,
+                                        float *value) {
+  if (!c || c->building || n < 0 || (n && (!xyz || !found || !value))) {
+    set_error("irt_debug_locate_sampler: bad argument");
+    return IRT_E_INVALID;
+  }
+  if (mode != IRT_MODE_CUBQL && mode != IRT_MODE_TRIANGLES) {
+    set_error("irt_debug_locate_sampler: sampler mode %d is neither IRT_MODE_CUBQL nor IRT_MODE_TRIANGLES", mode);
+    return IRT_E_INVALID;
+  }
+  if (c->updPending) return update_pending("irt_debug_locate_sampler");
+  if (c->wG == 0 && c->n != 0) {
+    set_error("irt_debug_locate_sampler: sampler mode %d needs irt_build_wedge_accel first", mode);
+    return IRT_E_INVALID;
+  }
+  if (n == 0) return IRT_OK;
+  IRT_HIP(hipSetDevice(c->device));
+  RenderArgs A;
+  memset(&A, 0, sizeof(A));
+  A.numCells = c->n;
+  A.sampler = mode;
+  A.wG = c->wG;
+  A.wOff = c->d_wOff;
+  A.wRec = c->d_wRec;
+  A.wBox = c->d_wBox;
+  A.wTrig = c->d_wTrig;
+  A.blocks = c->d_blocks;
+  float *d = nullptr;
+  IRT_HIP(hipMalloc((void **)&d, (size_t)n * 5 * sizeof(float)));
+  hipError_t e = hipMemcpy(d, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice);
+  int *dFound = reinterpret_cast<int *>(d + 3 * (size_t)n);
+  float *dValue = d + 4 * (size_t)n;
+  if (e == hipSuccess) {
+    launch_debug_locate_sampler(A, d, n, dFound, dValue, 0);
+    e = hipGetLastError();
+  }
+  e = e == hipSuccess ? hipMemcpy(found, dFound, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) : e;
+  e = e == hipSuccess ? hipMemcpy(value, dValue, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) : e;
+  (void)hipFree(d);
+  if (e != hipSuccess) {
+    set_error("irt_debug_locate_sampler: %s", hipGetErrorString(e));
+    return IRT_E_HIP;
+  }
+  return IRT_OK;
+}
+
 extern "C" int irt_debug_sched(irt_context *c, int *policy, int *lastApplied, long long *applied) {
   if (!c || !policy || !lastApplied || !applied) {
     set_error("irt_debug_sched: null argument");

@@ -200,6 +200,10 @@ void launch_render(const RenderArgs &A, int numBlocks, hipStream_t s, int varian
 void prewarm_render(int variant, hipStream_t s);
 void launch_debug_locate(const RenderArgs &A, const float *xyz, int n, int *found, float *value,
                          hipStream_t s, bool wave);
+// the unstructured samplers' point location (A.sampler: IRT_MODE_CUBQL or IRT_MODE_TRIANGLES)
+// through the Tracer of their sphere-accel launches; value[i] is 0 where found[i] is
+void launch_debug_locate_sampler(const RenderArgs &A, const float *xyz, int n, int *found, float *value,
+                                 hipStream_t s);
 void launch_shell_init(float *valueRanges, size_t numMCs, hipStream_t s);
 // rects (null: not kept): per record its clamped shell rectangle {ylo, yhi, zlo, zhi}, ylo > yhi
 // for a record that rasterises nothing -- what launch_shell_rebuild needs of the records

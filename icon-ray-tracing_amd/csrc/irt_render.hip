@@ -2737,6 +2737,34 @@ void launch_debug_locate(const RenderArgs &A, const float *xyz, int n, int *foun
     hipLaunchKernelGGL(k_debug_locate, dim3((n + 255) / 256), dim3(256), 0, s, A, xyz, n, found, value);
 }
 
+// The unstructured samplers' point location (Tracer::locate_wedge for IRT_MODE_CUBQL,
+// Tracer::locate_tri for IRT_MODE_TRIANGLES, chosen by A.sampler) on given points, through the
+// Tracer instantiation kernel_for picks for their sphere-accel launches (kSamplerVariant): the
+// frames' own code on records and points a frame almost never samples
+// (tests/test_gpu_samplers.py).
+constexpr int kSamplerVariant =
+    ((kDefaultVariant & ~4096) & ~(0xF00 | OPT_WAVEWG | OPT_WAVEWG2 | OPT_LEAN)) | OPT_WEDGE;
+__global__ void __launch_bounds__(256) k_debug_locate_sampler(RenderArgs A, const float *xyz, int n,
+                                                              int *found, float *value) {
+  __shared__ uint32_t s_cnt[kCnt];
+  if (threadIdx.x < kCnt) s_cnt[threadIdx.x] = 0;
+  __syncthreads();
+  Tracer<kSamplerVariant> T{{}, A, nullptr, nullptr, s_cnt, {0, 0, 0, 0, 0, 0, 0}};
+  const int j = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (j < n) {
+    float v = 0.f;
+    const bool f = T.locate(xyz[3 * j], xyz[3 * j + 1], xyz[3 * j + 2], v);
+    found[j] = f ? 1 : 0;
+    value[j] = f ? v : 0.f;
+  }
+}
+
+void launch_debug_locate_sampler(const RenderArgs &A, const float *xyz, int n, int *found, float *value,
+                                 hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_debug_locate_sampler, dim3((n + 255) / 256), dim3(256), 0, s, A, xyz, n, found, value);
+}
+
 // ------------------------------------------------------------------ variants / launcher
 // Variant bits: irt_render.hip OPT_* (bits 8-11: minimum waves per SIMD asked of the
 // register allocator).  OPT_MONO (4096) is kept in the numbering of round 1 (the one-kernel
@@ -2834,6 +2862,7 @@ RenderKernel kernel_for(const RenderArgs &A, int &threads) {
   constexpr int D = kDefaultVariant & ~OPT_MONO;
   constexpr int DB = D & ~(0xF00 | OPT_WAVEWG | OPT_WAVEWG2 | OPT_LEAN);  // 256-thread workgroups, full LDS
   constexpr int DW = DB | OPT_WEDGE | (K & OPT_SERIAL);
+  static_assert(DW == (kSamplerVariant | (K & OPT_SERIAL)), "k_debug_locate_sampler runs the samplers' Tracer");
   constexpr int DG = DB | 0x400;  // the grid-accel raygen: 4 waves/SIMD as measured in round 2
   const bool g = A.accelMode == IRT_ACCEL_GRID;
   threads = 256;

@@ -764,6 +764,20 @@ class Context:
         _check(lib().irt_build_wedge_accel(self._h, _ptr(cells), cells.size),
                "irt_build_wedge_accel")
 
+    def locate_sampler(self, points: np.ndarray, mode: int) -> tuple[np.ndarray, np.ndarray]:
+        """irt_debug_locate_sampler: the device point location of the MODE_CUBQL or
+        MODE_TRIANGLES sampler at points (n, 3); returns (found int32, value float32, 0 on a
+        miss).  Needs build_wedge_accel first."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        found = np.zeros(len(pts), np.int32)
+        value = np.zeros(len(pts), np.float32)
+        L = lib()
+        L.irt_debug_locate_sampler.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_void_p]
+        _check(L.irt_debug_locate_sampler(self._h, int(mode), _ptr(pts), len(pts), _ptr(found),
+                                          _ptr(value)), "irt_debug_locate_sampler")
+        return found, value
+
     def grid(self) -> tuple[np.ndarray, np.ndarray]:
         """GRID_ACCEL_MODE grid: (valueRanges (256^3, 2), maxOpacities (256^3,))."""
         n = 256 ** 3

@@ -149,6 +149,13 @@ int irt_debug_locate(irt_context *ctx, const float *xyz, int n, int *found, floa
  * the first candidates tested per lane, the rest dealt out over the wave, the second pass
  * for points exactly on a radial bin edge.  Must equal irt_debug_locate point for point. */
 int irt_debug_locate_wave(irt_context *ctx, const float *xyz, int n, int *found, float *value);
+/* The unstructured samplers' point location for n points: mode IRT_MODE_CUBQL runs
+ * Tracer::locate_wedge, IRT_MODE_TRIANGLES Tracer::locate_tri, in the Tracer instantiation their
+ * sphere-accel frames run, over the context's own wedge locator and height/value blocks:
+ * found[i] 0/1, value[i] (0 where found[i] is).  IRT_E_INVALID for any other mode, without
+ * irt_build_wedge_accel, or while a value update is pending, as irt_render; n == 0 is IRT_OK. */
+int irt_debug_locate_sampler(irt_context *ctx, int mode, const float *xyz, int n, int *found,
+                             float *value);
 /* Measured-cost scheduling state: the policy (IRT_SCHED; 0 = off), whether the last launch
  * ran its workgroups in a measured-cost order, and how many launches have. */
 int irt_debug_sched(irt_context *ctx, int *policy, int *lastApplied, long long *applied);

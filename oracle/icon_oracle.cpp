@@ -623,7 +623,26 @@ struct Scene {
   std::vector<float> rr;           // fast mode: {height[0], height[numLayers]} per record
   std::vector<Tri> tris;           // TRIANGLE_MODE only
   bool useTriangles = false;
+  // CUBQL_MODE: per record its first wedge and the union of its wedges' boxes (wedgeFirst has
+  // n + 1 entries).  A point outside the union is in none of the record's boxes, so skipping
+  // the record leaves the scan's answer -- the first accepting wedge in index order -- as it is.
+  std::vector<uint32_t> wedgeFirst;
+  std::vector<B3> wedgeRecBox;
 };
+
+void buildWedgeRecords(Scene &S) {
+  S.wedgeFirst.assign(S.n + 1, 0);
+  S.wedgeRecBox.assign(S.n, B3{v3(1e31f), v3(-1e31f)});
+  uint32_t w = 0;
+  for (size_t i = 0; i < S.n; ++i) {
+    S.wedgeFirst[i] = w;
+    for (int h = 0; h < S.cells[i].numLayers; ++h, ++w) {
+      S.wedgeRecBox[i].lower = vmin(S.wedgeRecBox[i].lower, S.wedges[w].box.lower);
+      S.wedgeRecBox[i].upper = vmax(S.wedgeRecBox[i].upper, S.wedges[w].box.upper);
+    }
+  }
+  S.wedgeFirst[S.n] = w;
+}
 
 void buildTriangles(Scene &S) {
   S.tris.resize(S.n);
@@ -819,8 +838,13 @@ inline bool sampleGrid(const Scene &S, V3 pos, float &value) {
 inline bool sampleVolume(const Scene &S, V3 pos, float &value) {
   if (S.useTriangles) return sampleTriangles(S, pos, value);  // TRIANGLE_MODE
   if (S.useWedges) {  // CUBQL_MODE (deviceCode.cu:90-115)
-    for (const Wedge &wd : S.wedges)
-      if (boxContains(wd.box, pos) && intersectWedgeEXT(value, pos, wd.v)) return true;
+    for (size_t i = 0; i < S.n; ++i) {
+      if (!boxContains(S.wedgeRecBox[i], pos)) continue;
+      for (uint32_t w = S.wedgeFirst[i]; w < S.wedgeFirst[i + 1]; ++w) {
+        const Wedge &wd = S.wedges[w];
+        if (boxContains(wd.box, pos) && intersectWedgeEXT(value, pos, wd.v)) return true;
+      }
+    }
     return false;
   }
   if (S.fast == 2) return sampleGrid(S, pos, value);
@@ -1294,6 +1318,7 @@ void prepare(Scene &S, const oc_params *p, int nthreads) {
   if (p && p->mode == 2 && !S.useWedges) {
     S.useWedges = true;
     buildWedges(S.cells, S.n, S.wedges);
+    buildWedgeRecords(S);
   }
   if (p && p->mode == 1 && !S.useTriangles) {
     S.useTriangles = true;
@@ -1506,10 +1531,32 @@ int oracle_intersect_wedge(const float *v24, oc_vec3 p, float *value) {
   return hit;
 }
 
-int oracle_wedge_sample(const oc_cell *cells, size_t n, oc_vec3 p, float *value) {
+// sampleVolume of a built scene at npts points: found[k] and the hit's value[k] (0 on a miss)
+static void samplePoints(const Scene &S, const float *pts, int npts, int32_t *found, float *value) {
+  for (int k = 0; k < npts; ++k) {
+    float v = 0.f;
+    found[k] = sampleVolume(S, V3{pts[3 * k], pts[3 * k + 1], pts[3 * k + 2]}, v) ? 1 : 0;
+    value[k] = found[k] ? v : 0.f;
+  }
+}
+
+int oracle_wedge_sample_points(const oc_cell *cells, size_t n, const float *pts, int npts,
+                               int32_t *found, float *value) {
+  if (npts < 0) return -1;
   Scene S{cells, n, 0, {}, {}, {}, true, {}, {}, false};
   buildWedges(cells, n, S.wedges);
-  return sampleVolume(S, toV3(p), *value);
+  buildWedgeRecords(S);
+  samplePoints(S, pts, npts, found, value);
+  return 0;
+}
+
+int oracle_wedge_sample(const oc_cell *cells, size_t n, oc_vec3 p, float *value) {
+  int32_t found = 0;
+  float v = 0.f;
+  const float xyz[3] = {p.x, p.y, p.z};
+  oracle_wedge_sample_points(cells, n, xyz, 1, &found, &v);
+  if (found) *value = v;
+  return found;
 }
 
 int oracle_sample_volume(const oc_cell *cells, size_t n, int fast, const float *pts, int npts,
@@ -1525,10 +1572,22 @@ int oracle_sample_volume(const oc_cell *cells, size_t n, int fast, const float *
   return 0;
 }
 
-int oracle_triangle_sample(const oc_cell *cells, size_t n, oc_vec3 p, float *value) {
+int oracle_triangle_sample_points(const oc_cell *cells, size_t n, const float *pts, int npts,
+                                  int32_t *found, float *value) {
+  if (npts < 0) return -1;
   Scene S{cells, n, 0, {}, {}, {}, false, {}, {}, true};
   buildTriangles(S);
-  return sampleVolume(S, toV3(p), *value);
+  samplePoints(S, pts, npts, found, value);
+  return 0;
+}
+
+int oracle_triangle_sample(const oc_cell *cells, size_t n, oc_vec3 p, float *value) {
+  int32_t found = 0;
+  float v = 0.f;
+  const float xyz[3] = {p.x, p.y, p.z};
+  oracle_triangle_sample_points(cells, n, xyz, 1, &found, &v);
+  if (found) *value = v;
+  return found;
 }
 
 float oracle_linear_to_srgb(float x) { return linear_to_srgb(x); }

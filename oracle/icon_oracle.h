@@ -166,6 +166,12 @@ int oracle_dda3_trace(oc_vec3 org, oc_vec3 dir, float tmin, float tmax, const in
 int oracle_intersect_wedge(const float *v24, oc_vec3 p, float *value);
 /* CUBQL_MODE sampleVolume over the wedges of `cells` (hostCode.cu:557-600). */
 int oracle_wedge_sample(const oc_cell *cells, size_t n, oc_vec3 p, float *value);
+/* The same at npts points (xyz) with the wedges built once: found[k] and the hit's value[k]
+   (0 on a miss); likewise TRIANGLE_MODE below.  Return 0, -1 on bad arguments. */
+int oracle_wedge_sample_points(const oc_cell *cells, size_t n, const float *pts, int npts,
+                               int32_t *found, float *value);
+int oracle_triangle_sample_points(const oc_cell *cells, size_t n, const float *pts, int npts,
+                                  int32_t *found, float *value);
 /* The default (USER_GEOM) sampleVolume over `cells` (deviceCode.cu:116-123) at npts points
    (xyz): found[k] and the first hit's value[k] (0 on a miss).  fast as oracle_render: 0 the
    literal sample(), 1 the scan over precomputed planes, 2 the direction-voxel locator. */

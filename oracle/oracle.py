@@ -101,6 +101,8 @@ def olib() -> C.CDLL:
         L.oracle_intersect_wedge.argtypes = [P, OVec3, C.POINTER(C.c_float)]
         L.oracle_wedge_sample.argtypes = [P, S, OVec3, C.POINTER(C.c_float)]
         L.oracle_triangle_sample.argtypes = [P, S, OVec3, C.POINTER(C.c_float)]
+        L.oracle_wedge_sample_points.argtypes = [P, S, P, I, P, P]
+        L.oracle_triangle_sample_points.argtypes = [P, S, P, I, P, P]
         L.oracle_sample_volume.argtypes = [P, S, I, P, I, P, P]
         L.oracle_linear_to_srgb.argtypes = [F]
         L.oracle_linear_to_srgb.restype = F
@@ -340,6 +342,43 @@ def sample_volume(cells: np.ndarray, pts: np.ndarray, fast: int = 1):
     rc = olib().oracle_sample_volume(_p(cells), cells.size, fast, _p(pts), len(pts), _p(found),
                                      _p(value))
     assert rc == 0
+    return found, value
+
+
+def _sample_points(entry, cells: np.ndarray, pts: np.ndarray):
+    cells = np.ascontiguousarray(cells, dtype=CELL_DTYPE)
+    pts = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+    found = np.zeros(len(pts), np.int32)
+    value = np.zeros(len(pts), np.float32)
+    rc = entry(_p(cells), cells.size, _p(pts), len(pts), _p(found), _p(value))
+    assert rc == 0
+    return found, value
+
+
+def wedge_sample_points(cells: np.ndarray, pts: np.ndarray):
+    """CUBQL_MODE sampleVolume (the brute-force scan over every wedge, built once) at pts (n,3);
+    returns (found int32, value float32, 0 on a miss)."""
+    return _sample_points(olib().oracle_wedge_sample_points, cells, pts)
+
+
+def triangle_sample_points(cells: np.ndarray, pts: np.ndarray):
+    """TRIANGLE_MODE sampleVolume (the scan over every bottom triangle) at pts (n,3); returns
+    (found int32, value float32, 0 on a miss)."""
+    return _sample_points(olib().oracle_triangle_sample_points, cells, pts)
+
+
+def ref_wedge_sample_points(cells: np.ndarray, pts: np.ndarray):
+    """The reference's own wedge scan (oracle/_ref, ref_wedge_sample) at pts (n,3), one point at
+    a time; returns (found int32, value float32, 0 on a miss).  Fixture generation only."""
+    cells = np.ascontiguousarray(cells, dtype=CELL_DTYPE)
+    pts = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+    found = np.zeros(len(pts), np.int32)
+    value = np.zeros(len(pts), np.float32)
+    for k, p in enumerate(pts):
+        v = C.c_float(0)
+        p = np.ascontiguousarray(p)
+        found[k] = rlib().ref_wedge_sample(_p(cells), cells.size, _p(p), C.byref(v))
+        value[k] = v.value if found[k] else 0.0
     return found, value
 
 

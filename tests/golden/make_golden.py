@@ -12,7 +12,8 @@ reference functions (LCG, sample, findHeight, intersectSphere, boxTest, sdda,
 linear_to_srgb/make_rgba, toSpherical/toCartesian, getBounds, resampleLUT, Camera);
 kats_grid.npz + f6_*_grid.npz the GRID_ACCEL_MODE path (dda3, buildGrid_ICON, a frame);
 kats_wedge.npz + f7_*_wedge.npz the CUBQL_MODE sampler (intersectWedgeEXT, the wedge
-sampleVolume, a frame).
+sampleVolume, a frame); kats_wedge_edges.npz (`make_golden.py wedge_edges`) the wedge
+sampleVolume on the edge records and points of tests/sampler_scenes.py.
 f8_terrain_*.npz + kats_terrain.npz (`make_golden.py terrain`, which writes these files only)
 pin the record layout convert_icon writes for real fields -- terrain-following heights, an
 inverted first layer over land (height[0] > height[1]), zero-thickness top records (65
@@ -422,6 +423,38 @@ def make_wedge_fixtures():
     # one CUBQL_MODE frame
     make_frame("f7_r2b02_l20_wedge", (2, 2, 20, -1, 64, 64, FRAMING, (0,), 0, "default"),
                mode=2)
+    make_wedge_edge_fixture()
+
+
+WEDGE_EDGE_SCENES = ("heights", "nonfinite", "convert_icon")  # of tests/sampler_scenes.py
+WEDGE_EDGE_POINTS = 1000  # per scene, a seeded subset of sampler_scenes.points(name)
+
+
+def make_wedge_edge_fixture():
+    """kats_wedge_edges.npz (`make_golden.py wedge_edges` writes this file only): the reference's
+    wedge sampleVolume (ref_wedge_sample) on the edge records of tests/sampler_scenes.py --
+    unsorted, reversed and repeated heights, records of 0, 1 and 2 layers, NaN / inf / FLT_MAX
+    values, the convert_icon layout -- at a subset of those scenes' points.  Per scene: the
+    records as bytes (transposed: byte k of every record in row k), the points, their indices in the scene's point set, hit and value."""
+    import sampler_scenes as S
+    out = {}
+    for name in WEDGE_EDGE_SCENES:
+        cells, ps = S.scene(name), S.points(name)
+        rng = np.random.default_rng(20261019)
+        pick = np.sort(rng.choice(len(ps.points), WEDGE_EDGE_POINTS, replace=False))
+        pts = np.ascontiguousarray(ps.points[pick])
+        hit, val = O.ref_wedge_sample_points(cells, pts)
+        # the records' bytes transposed (284, n): byte planes deflate to about half
+        out.update({f"cells_{name}": np.ascontiguousarray(np.array(cells).view(np.uint8).reshape(cells.size, 284).T),
+                    f"points_{name}": pts, f"index_{name}": pick.astype(np.int32),
+                    f"hit_{name}": hit, f"value_{name}": val})
+        print(f"kats_wedge_edges {name}: {int(hit.sum())} of {len(pts)} hits, "
+              f"{int(np.isnan(val).sum())} NaN values")
+    path = os.path.join(HERE, "kats_wedge_edges.npz")
+    np.savez_compressed(path, **out)
+    n = os.path.getsize(path)
+    print(f"kats_wedge_edges.npz: {n} bytes")
+    assert n <= os.path.getsize(os.path.join(HERE, "kats_wedge.npz")), n
 
 
 TERRAIN_FRAMES = {
@@ -639,6 +672,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "wedge":
         make_wedge_fixtures()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "wedge_edges":
+        make_wedge_edge_fixture()
         sys.exit(0)
     for name, spec in FRAMES.items():
         make_frame(name, spec)

@@ -6,7 +6,11 @@ through the wedges of buildCuBQLAccel (hostCode.cu:557-600) and intersectWedgeEX
 outputs (tests/golden/kats_wedge.npz, f7_*_wedge.npz).  Bar: bit-exact.
 
 Parity note: cuBQL's BVH traversal order is not reproducible (the submodule is not
-vendored); both sides take the first accepting wedge in (cell, layer) order."""
+vendored); both sides take the first accepting wedge in (cell, layer) order.
+
+These are whole frames of flat grids.  The samplers' device point location is checked point by
+point, on edge records and edge points, in tests/test_gpu_samplers.py (scenes and points:
+tests/sampler_scenes.py; the host twins and the reference fixture: tests/test_samplers_cpu.py)."""
 import numpy as np
 import pytest
 
