@@ -114,6 +114,22 @@ inline bool update_range_ok(size_t first, size_t n, size_t numCells) {
   return first <= numCells && n <= numCells - first;
 }
 
+// Measured-cost scheduling (host/irt_sched.cpp): the words of one order buffer from the measured
+// costs of a frame's packets (cost: 4 per 256-pixel block, 64 per 64x64 tile).  out holds
+//   [0, cap)                    the block order: tiles, or bands of max(1, tilesX / tileStride)
+//                               tiles (policy 2), by descending summed cost (stable; policy 3:
+//                               reversed index order), each tile's 16 blocks together and ascending;
+//   [cap, cap + maxSplit)       the split work items, (packet << 8) | (part << 4) | splitLg, the
+//                               parts of one packet 8 items apart, ~0u for an empty item;
+//   (4 cap + 31) / 32 more      the bitmap of the split packets.
+// A packet is split when its cost exceeds splitFactor x the frame's ideal span (the costs' sum over
+// 20 numCU resident waves) -- costliest first, at most a tenth of the packets and maxSplit items,
+// only with one-wave workgroups (wavewg) and splitLg > 0.  cap >= numBlocks, a multiple of 16.
+// Returns the number of work items (a multiple of 8).
+uint32_t sched_order(const uint32_t *cost, int numBlocks, int tilesX, int tileStride, int policy,
+                     int splitLg, float splitFactor, int numCU, bool wavewg, size_t cap,
+                     uint32_t maxSplit, uint32_t *out);
+
 // Synthetic RnBk grid generator (host/irt_synth.cpp): open once, fill any record range.
 int synth_open(int rootN, int bisections, int levels, float topHeight, float noise, uint32_t seed,
                float terrainHeight,

@@ -193,4 +193,17 @@ int irt_debug_intersect_wedge(const float *v24, irt_vec3f p, float *value) {
   return hit ? 1 : 0;
 }
 
+int irt_debug_sched_order(const uint32_t *cost, int numBlocks, int tilesX, int tileStride, int policy,
+                          int splitLg, float splitFactor, int numCU, int wavewg, size_t capacity,
+                          uint32_t maxSplit, uint32_t *out, uint32_t *numSplit) {
+  if (!cost || !out || !numSplit || numBlocks < 0 || numBlocks % 16 || (size_t)numBlocks > capacity ||
+      splitLg < 0 || splitLg > 3 || maxSplit % 8) {
+    set_error("irt_debug_sched_order: bad argument");
+    return IRT_E_INVALID;
+  }
+  *numSplit = sched_order(cost, numBlocks, tilesX, tileStride, policy, splitLg, splitFactor, numCU,
+                          wavewg != 0, capacity, maxSplit, out);
+  return IRT_OK;
+}
+
 }  // extern "C"

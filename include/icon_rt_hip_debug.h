@@ -178,6 +178,16 @@ long long irt_debug_launch_workgroups(const irt_context *ctx, int numTiles, int 
  * per part, and the items are padded with empty ones to a multiple of 8 (so *numSplit is parts x
  * packets rounded up, not the packet count) -- and splitLg.  Frames are unchanged. */
 int irt_debug_sched_split(const irt_context *ctx, int *numSplit, int *splitLg);
+/* The host computation behind both (host/irt_sched.cpp; no context, no device): one order buffer
+ * from the measured costs of a frame's packets, cost[4 * numBlocks] (numBlocks a multiple of 16,
+ * at most capacity).  out must hold capacity + maxSplit + (4 * capacity + 31) / 32 words: the
+ * block order (numBlocks words used), the split work items ((packet << 8) | (part << 4) | splitLg,
+ * ~0u: empty; *numSplit of them, a multiple of 8) and the bitmap of the split packets.  policy as
+ * IRT_SCHED; wavewg: the launch runs one-wave workgroups (no splits otherwise); maxSplit: most
+ * work items, a multiple of 8 (the library passes 4096). */
+int irt_debug_sched_order(const uint32_t *cost, int numBlocks, int tilesX, int tileStride, int policy,
+                          int splitLg, float splitFactor, int numCU, int wavewg, size_t capacity,
+                          uint32_t maxSplit, uint32_t *out, uint32_t *numSplit);
 /* Chained progressive frames on (default; IRT_CHAIN=0 turns it off per context) or off: a
  * launch of several frames (irt_render_accumulate, irt_render_tiles_accumulate,
  * irt_render_tile_list) lerps each frame straight into accum/fb, frame f's workgroup waiting for
