@@ -258,7 +258,10 @@ __device__ __forceinline__ uint32_t make_8bit(float f) {
 // the number of thresholds <= x.  The hardware log2/exp2 estimate of the expression
 // (dvr_course-common-both.h:29-34, 89-92) is within one byte of it; the thresholds then
 // settle the exact count (two independent LDS reads instead of an 8-step binary search).
+// From th[0] on (about 3.7e16, +inf included) the expression's int conversion overflows and the
+// byte is 0, as make_8bit gives it for alpha.
 __device__ __forceinline__ uint32_t srgb_byte(const float *th, float x) {
+  const float over = th[0];
   const float s = x <= 0.0031308f
                       ? 12.92f * x
                       : 1.055f * __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(x) * (1.f / 2.4f)) - 0.055f;
@@ -271,7 +274,7 @@ __device__ __forceinline__ uint32_t srgb_byte(const float *th, float x) {
     --b;
     while (b > 0 && !(th[b] <= x)) --b;
   }
-  return (uint32_t)b;
+  return x >= over ? 0u : (uint32_t)b;
 }
 
 }  // namespace irt

@@ -76,7 +76,8 @@ void volume_acc_finish(const VolumeAcc &a, irt_volume_info &info);
 const std::vector<float> &logf_table();
 
 // th[b] (b = 1..255) = smallest float x with make_8bit(linear_to_srgb(x)) >= b, under the
-// host glibc powf (dvr_course-common-both.h:30-35, 89-92); th[0] = -inf.
+// host glibc powf (dvr_course-common-both.h:30-35, 89-92); th[0] = smallest float x >= 1 whose
+// byte is 0 again: int(s * 256) overflows there (cvttss2si: INT_MIN), +inf included.
 void srgb_thresholds(float th[256]);
 
 // Host restatement of the scalar reference functions the kernels rely on, for checks.

@@ -234,7 +234,20 @@ static uint32_t srgb_byte(float x) {
 }
 
 void srgb_thresholds(float th[256]) {
-  th[0] = -INFINITY;
+  // th[0]: past 1 the byte stays 255 until s * 256 reaches 2^31, where cvttss2si answers INT_MIN
+  // and the byte is 0 -- +inf included (an accum buffer handed in with such values).  The smallest
+  // such float, by the same search over [1, +inf].
+  {
+    uint32_t lo = 0x3f800000u, hi = 0x7f800000u;  // byte(1.0f) == 255, byte(+inf) == 0
+    while (lo < hi) {
+      uint32_t mid = lo + (hi - lo) / 2;
+      if (srgb_byte(u2f(mid)) == 0u)
+        hi = mid;
+      else
+        lo = mid + 1;
+    }
+    th[0] = u2f(lo);
+  }
   // byte(x) is monotone non-decreasing in x (tests/test_host_tables.py sweeps every
   // float in [0,1] to confirm under this libm); binary-search each step on the ordered
   // bit patterns of non-negative floats.

@@ -23,6 +23,9 @@ f9_view_*.npz (`make_golden.py views`): four frames of the terrain scene from ca
 helpers.view_battery -- inside the shell, under it, south of the globe (AE) and along the horizon
 (grid).  Seventeen golden frames in all (f1 x 2, f2..f7, f8 x 5, f9 x 4) come from the reference's
 own code.
+ragged_frames.npz (`make_golden.py ragged`): eight more reference frames in one file, at 37 x 29
+and 67 x 33 -- sizes that are no multiples of 8, where the frame edge cuts the kernels' 8 x 8
+packets -- which pin the oracle the ragged-frame GPU tests compare with.
 The `.ic` inputs are synthetic grids from icon-ray-tracing_amd's generator (real DWD data
 is not available offline); they are stored verbatim, so the fixtures do not depend on it.
 """
@@ -57,7 +60,9 @@ SPARSE_LUT5 = np.array([[0.1, 0.2, 0.9, 0.05], [0.9, 0.9, 0.2, 0.02], [0.8, 0.1,
                        np.float32)
 
 
-def make_frame(name, spec, mode=0, check=None, accel_mode=0):
+def make_frame(name, spec, mode=0, check=None, accel_mode=0, save=True, each=None):
+    """save=False: nothing is written, the fixture's arrays are returned; each: a list that gets
+    (accum, fb) copies after every accumID."""
     rn, bis, L, cap, W, H, cam, ids, raygen, tf = spec[:10]
     terrain = float(spec[10]) if len(spec) > 10 else 0.0
     cells = irt.synth_grid(rn, bis, L, noise=0.1 if tf == "sparse" else 0.0, terrain=terrain)
@@ -120,6 +125,8 @@ def make_frame(name, spec, mode=0, check=None, accel_mode=0):
         p.accumID = aid
         _, _, c = O.ref_render(S, p, W, H, accum=accum, fb=fb, threads=1)
         counts.append(c.copy())
+        if each is not None:
+            each.append((accum.copy(), fb.copy()))
     out = dict(
         cells=cells.view(np.uint8).reshape(cells.size, 284),
         width=W, height=H, camera12=cam12, accum_ids=np.array(ids, np.int32), raygen=raygen,
@@ -131,6 +138,8 @@ def make_frame(name, spec, mode=0, check=None, accel_mode=0):
         out["accel_mode"] = accel_mode
     if check is not None:
         check(name, cells, out)  # before anything is written
+    if not save:
+        return out
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
     print(f"{name}: {cells.size} records {W}x{H}, hit {(accum[..., 3] > 0).mean():.3f}, "
           f"samples {counts}")
@@ -658,9 +667,41 @@ def make_view_fixtures():
         assert n <= min(largest, 1 << 20), (name, n, largest)
 
 
+RAGGED_SIZES = ((37, 29), (67, 33))  # no multiples of 8: the frame edge cuts 8 x 8 packets
+
+
+def make_ragged_fixture():
+    """ragged_frames.npz (`make_golden.py ragged` writes this file only): the reference's raygen
+    on the flat scene of tests/ragged_scenes.py, synth_grid(2, 1, 20), at sizes that are no
+    multiples of 8, under FRAMING and viewAll, accumIDs 0 and 1: accum, fb and (sampleVolume calls,
+    found) after each frame.  The scene's inputs are stored once (records as transposed bytes),
+    the camera per frame."""
+    out = {}
+    for W, H in RAGGED_SIZES:
+        for tag, cam in (("framing", FRAMING), ("viewall", None)):
+            each = []
+            d = make_frame("", (2, 1, 20, -1, W, H, cam, (0, 1), 0, "default"), save=False, each=each)
+            if not out:
+                out.update(cells=np.ascontiguousarray(d["cells"].T), lut=d["lut"], value_range=d["value_range"],
+                           opacity_scale=d["opacity_scale"], unit_distance=d["unit_distance"],
+                           raygen=d["raygen"], accum_ids=d["accum_ids"])
+            key = f"{W}x{H}_{tag}"
+            out.update({f"camera12_{key}": d["camera12"], f"accum_{key}": np.array([e[0] for e in each]),
+                        f"fb_{key}": np.array([e[1] for e in each]), f"counts_{key}": d["counts"]})
+            print(f"ragged {key}: hit {(each[-1][0][..., 3] > 0).mean():.3f}, counts {d['counts'].tolist()}")
+    path = os.path.join(HERE, "ragged_frames.npz")
+    np.savez_compressed(path, **out)
+    n = os.path.getsize(path)
+    print(f"ragged_frames.npz: {n} bytes")
+    assert n <= 1 << 19, n
+
+
 if __name__ == "__main__":
     if not O.have_ref():
         sys.exit("oracle/_ref/libiconref.so missing: make -C oracle ref (needs /root/reference)")
+    if len(sys.argv) > 1 and sys.argv[1] == "ragged":
+        make_ragged_fixture()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "terrain":
         make_terrain_fixtures()
         sys.exit(0)
@@ -683,3 +724,4 @@ if __name__ == "__main__":
     make_wedge_fixtures()
     make_terrain_fixtures()
     make_view_fixtures()
+    make_ragged_fixture()

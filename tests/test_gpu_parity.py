@@ -913,7 +913,8 @@ def test_device_srgb_byte_equals_threshold_count():
     """csrc/irt_device.h srgb_byte (hardware log2/exp2 estimate, then settled on the host
     thresholds) == the number of thresholds <= x, which test_host_logic pins to the
     reference's make_8bit(linear_to_srgb(x)): every threshold and its float neighbours,
-    a dense sweep, random values, specials."""
+    a dense sweep, random values, specials -- and 0 from th[0] on (+inf included), where the
+    reference's int conversion overflows (test_host_logic pins th[0] too)."""
     L = irt.lib()
     L.irt_debug_device_srgb.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     th = np.zeros(256, np.float32)
@@ -925,12 +926,16 @@ def test_device_srgb_byte_equals_threshold_count():
     x = np.concatenate([near, np.linspace(-0.05, 1.05, 1 << 20, dtype=np.float32),
                         rng.random(1 << 20, dtype=np.float32),
                         rng.random(1 << 16, dtype=np.float32) * np.float32(1e-3),
-                        np.float32([0.0, -0.0, 0.0031308, 1.0, 2.0, -1.0, 1e-30, np.nan, np.inf, -np.inf])])
+                        np.float32([0.0, -0.0, 0.0031308, 1.0, 2.0, -1.0, 1e-30, np.nan, np.inf, -np.inf]),
+                        # th[0]: from there on the reference's int conversion overflows, byte 0
+                        np.float32([th[0], np.nextafter(th[0], np.float32(0)),
+                                    np.nextafter(th[0], np.float32(np.inf)), 1e16, 1e17, 3.4e38])])
     x = x.astype(np.float32)
     out = np.zeros(x.size, np.uint32)
     assert L.irt_debug_device_srgb(0, x.ctypes.data, out.ctypes.data, x.size) == 0, L.irt_last_error()
     want = np.searchsorted(t, x, side="right").astype(np.uint32)
     want[np.isnan(x)] = 0
+    want[x >= th[0]] = 0
     bad = np.nonzero(out != want)[0]
     assert bad.size == 0, (x[bad[:5]], out[bad[:5]], want[bad[:5]])
 

@@ -37,7 +37,8 @@ from test_gpu_scale import host_threads
 
 pytestmark = pytest.mark.gpu
 
-W, H = 88, 72  # ragged against 8x8 packets, 16x16 blocks and 64x64 tiles; not square
+W, H = 88, 72  # ragged against 16x16 blocks and 64x64 tiles, not against 8x8 packets (11 x 9 of them:
+#                tests/test_gpu_ragged.py has the sizes that cut packets); not square
 VIEWS = list(VIEW_NAMES)
 NOT_FRAMING = [v for v in VIEWS if v != "framing"]
 NOMISS, VOIDLOC = 262144, 1073741824

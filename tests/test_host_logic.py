@@ -169,6 +169,12 @@ def test_srgb_thresholds_reproduce_make_8bit():
         t = th[b]
         below = np.nextafter(t, np.float32(-1))
         assert byte(t) == ref_byte(float(t)) and byte(below) == ref_byte(float(below))
+    # th[0]: from there on (+inf included) int(s * 256) overflows and the reference's byte is 0
+    over = th[0]
+    assert 1e16 < over < 1e17
+    assert ref_byte(float(np.nextafter(over, np.float32(0)))) == 255 and ref_byte(float(over)) == 0
+    for x in np.float32([1e16, 3e16, 1e17, 1e30, 3.4e38, np.inf]):
+        assert ref_byte(float(x)) == (0 if x >= over else 255), x
 
 
 @pytest.mark.parametrize("rn,bis,L", [(1, 0, 4), (2, 2, 40), (2, 3, 90)])

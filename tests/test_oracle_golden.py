@@ -37,6 +37,35 @@ def test_frame_fixture(name, locator):
     assert np.array_equal(fb, d["fb"])
 
 
+@pytest.mark.parametrize("locator", [1, 2], ids=["scan", "dirgrid"])
+@pytest.mark.parametrize("key", ["37x29_framing", "37x29_viewall", "67x33_framing", "67x33_viewall"])
+def test_ragged_frame_fixture(key, locator):
+    """ragged_frames.npz: the reference's own frames at sizes that are no multiples of 8 (the seed
+    accumID * W * H + x with W * H odd, pixelID = x + W * y with W odd), accumIDs 0 and 1 on the
+    same buffers: the oracle's accum bits, fb words and counts after each frame.  This pins the
+    oracle that tests/test_gpu_ragged.py compares the device with, on the flat scene of
+    tests/ragged_scenes.py -- whose records the fixture holds, and which the scene must equal."""
+    import os
+    import ragged_scenes
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ragged_frames.npz"))
+    d = {k: z[k] for k in z.files}
+    d["cells"] = np.ascontiguousarray(d["cells"].T).view(O.CELL_DTYPE).ravel()
+    assert d["cells"].tobytes() == ragged_scenes.cells("flat").tobytes()
+    S = oracle_scene(d)
+    W, H = (int(v) for v in key.split("_")[0].split("x"))
+    d["camera12"] = d["camera12_" + key]
+    accum = np.zeros((H, W, 4), np.float32)
+    fb = np.zeros((H, W), np.uint32)
+    assert list(d["accum_ids"]) == [0, 1]
+    for k, aid in enumerate(d["accum_ids"]):
+        _, _, st = S.render(params(S, d, aid), W, H, accum=accum, fb=fb, threads=4, fast=locator)
+        assert (st.locate_calls, st.samples_found) == tuple(int(c) for c in d["counts_" + key][k])
+        assert st.rays_launched == W * H
+        assert np.array_equal(bits(accum), bits(d["accum_" + key][k]))
+        assert np.array_equal(fb, d["fb_" + key][k])
+    assert (d["accum_" + key][-1][..., 3] > 0).any()
+
+
 @pytest.mark.parametrize("name", ["f2_r2b02_l90"])
 def test_literal_sample_mode_matches_fixture(name):
     """The literal sample() (toSpherical incl. the dead asinf/atan2f, corners rebuilt per
