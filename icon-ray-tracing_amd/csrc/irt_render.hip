@@ -1441,15 +1441,86 @@ __device__ __forceinline__ float4 chain_load_accum(const RenderArgs &A, size_t o
   const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)A.accum, 0, (int)(out_pixels(A) * 16u), 0x00020000);
   return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(outIdx * 16u), 0, 16));
 }
+// Which frames of a chained launch leave fb alone.  In a launch of consecutive progressive frames
+// of one camera (irt_render_accumulate and its tile and tile-list forms: A.chain without
+// A.frameCams) a pixel's RGBA8 is make_rgba(linear_to_srgb(accum)) of the accum its frame just
+// stored, and every later frame of the launch whose ray hits the box overwrites it before anything
+// reads it: only the launch's last frame converts and stores it (every frame stores accum, the
+// hand-off, as before).  Everything else keeps the pixel write it had: a sequence of views
+// (A.frameCams: each view is an image of its own), single-frame launches and the unchained
+// sample-buffer batch (no A.chain; k_accumulate), and the split-packet and slot-table kernels
+// (OPT_SPLIT, single frames only; OPT_SLOT: render_pixel_coop leaves both out at compile time).
+__device__ __forceinline__ bool chain_skips_fb(const RenderArgs &A, int frame) {
+  return A.chain && !A.frameCams && frame < A.numSamples - 1;
+}
+// ... and the frame of such a launch that writes fb for all of them: its last
+__device__ __forceinline__ bool chain_last_fb(const RenderArgs &A, int frame) {
+  return A.chain && !A.frameCams && frame == A.numSamples - 1;
+}
+// The other half of that rule, for a pixel whose ray misses the box in the launch's last frame
+// (deviceCode.cu:294-295: that frame writes nothing).  When every frame wrote fb, the pixel then
+// held the bytes of the latest earlier frame of the launch whose ray hit -- the conversion of the
+// accum that frame stored, which no frame has touched since, so of accum as it is now.  The lane
+// replays gen_ray + box_test for frames frame - 1 .. 0 of the launch (the same code on the same
+// inputs as those frames' own waves: the same hit or miss), stops at the first hit and then writes
+// the conversion of accum[pixel], read past L1 after the wave's chain wait (frame - 1's publish word
+// covers every earlier frame's stores).  No frame of the launch hit: fb stays untouched.  Cold: a
+// camera with every ray in the box never gets here.
+__device__ __forceinline__ void chain_replay_fb(const RenderArgs &KA, uint32_t blk, int ptid, int frame,
+                                                const float *s_th) {
+  // The launch's arguments through a per-lane pointer, and the frame counter per lane: vector
+  // loads and VGPRs, free at the ray's end, where the kernel has no SGPRs to spare (the accum
+  // pixel by agent-scope loads, sc1 as chain_load_accum's, for the same reason: no resource words).
+  const RenderArgs *vp = &KA;
+  asm volatile("" : "+v"(vp));
+  const RenderArgs &A = *vp;
+  const Pixel p = pixel_of(A, blk, ptid);
+  if (!p.active) return;
+  int g = frame;
+  asm volatile("" : "+v"(g));
+  bool seen = false;
+#pragma nounroll
+  while (--g >= 0 && !seen) {
+    uint32_t st;
+    float dx, dy, dz, t0, t1;
+    gen_ray(A, A.accumID + g, p.x, p.y, st, dx, dy, dz);
+    const Ray ray = {A.org.x, A.org.y, A.org.z, 0.f, dx, dy, dz, 1e10f};
+    seen = box_test(ray, A, t0, t1);
+  }
+  if (!seen) return;
+  const float *ap = reinterpret_cast<const float *>(A.accum + p.outIdx);
+  float a[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) a[k] = __hip_atomic_load(ap + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const uint32_t rgba = srgb_byte(s_th, a[0]) + (srgb_byte(s_th, a[1]) << 8) + (srgb_byte(s_th, a[2]) << 16) +
+                        (make_8bit(a[3]) << 24);
+  __builtin_nontemporal_store(rgba, &A.fb[p.outIdx]);
+}
 // write_pixel's lerp and RGBA8 with the weight of this frame; publish: write-through (sc1)
-// stores that the next frame's wave reads, else streaming stores as write_pixel<true>
+// stores that the next frame's wave reads, else streaming stores as write_pixel<true>.
+// toFb (wave-uniform: a scalar branch) is false for a frame whose RGBA8 a later frame of the same
+// launch overwrites before anything reads it (chain_skips_fb): accum alone is stored, no
+// conversion runs.
 __device__ __forceinline__ void write_pixel_chain(const RenderArgs &A, size_t outIdx, float cr, float cg, float cb,
-                                                  float alpha, float w, const float *s_th, float4 old, bool publish) {
+                                                  float alpha, float w, const float *s_th, float4 old, bool publish,
+                                                  bool toFb) {
   float4 nv;
   nv.x = w * cr + (1.f - w) * old.x;
   nv.y = w * cg + (1.f - w) * old.y;
   nv.z = w * cb + (1.f - w) * old.z;
   nv.w = w * alpha + (1.f - w) * old.w;
+  if (!toFb) {
+    if (publish) {
+      const __amdgpu_buffer_rsrc_t ra =
+          __builtin_amdgcn_make_buffer_rsrc((void *)A.accum, 0, (int)(out_pixels(A) * 16u), 0x00020000);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, nv), ra, (int)(outIdx * 16u), 0, 16);
+    } else {
+      typedef float f4v __attribute__((ext_vector_type(4)));
+      const f4v t = {nv.x, nv.y, nv.z, nv.w};
+      __builtin_nontemporal_store(t, reinterpret_cast<f4v *>(&A.accum[outIdx]));
+    }
+    return;
+  }
   const uint32_t rgba = srgb_byte(s_th, nv.x) + (srgb_byte(s_th, nv.y) << 8) +
                         (srgb_byte(s_th, nv.z) << 16) + (make_8bit(nv.w) << 24);
 #ifdef IRT_PROBE_BUILD
@@ -2228,7 +2299,20 @@ __device__ __forceinline__ void render_pixel_coop(const RenderArgs &A, Tracer<OP
     const uint64_t ib = __ballot(inBox);  // rays in the box (T.count(1) at the box test)
     if (ib && __lane_id() == (unsigned)__builtin_ctzll(ib)) atomicAdd(&T.s_cnt[1], (uint32_t)__popcll(ib));
   }
-  if (!inBox) return;
+  // the pixel write decides here which launch forms skip a non-final frame's RGBA8 (chain_skips_fb:
+  // chained progressive frames of one camera); the split-packet kernels keep their code as it was,
+  // and so do the slot-table kernels, which write fb in every frame: with the skip and the replay
+  // their hole-free form spilled 69 SGPRs instead of 63 and ran 0.4 % slower one launch per frame
+  // at C3s and C5, with nothing gained chained (profiles/r07a_fbskip/)
+  constexpr bool kFbSkip = (OPT & (OPT_SPLIT | OPT_SLOT)) == 0;
+  if (!inBox) {
+    if constexpr (kFbSkip) {
+      // the launch's last frame, earlier ones having skipped fb: what an earlier hit left there
+      if (chain_last_fb(TA, frame))
+        chain_replay_fb(TA, (uint32_t)opaque_u((int)blk), ptid_late(), frame, s_th);
+    }
+    return;
+  }
   const int tl = tid_late();
   const float4 c = hit ? lds_ld16(&s_entry[tl]) : make_float4(0.f, 0.f, 0.f, 0.f);
   if (toSample) {
@@ -2250,7 +2334,7 @@ __device__ __forceinline__ void render_pixel_coop(const RenderArgs &A, Tracer<OP
       }
       // 1.f / (float)(accumID + 1) of this frame, correctly rounded as the host's TA.accumW
       write_pixel_chain(TA, outIdx, c.x, c.y, c.z, c.w, 1.f / (float)(accumID + 1), s_th, old,
-                        frame < TA.numSamples - 1 && pairPos != 1);
+                        frame < TA.numSamples - 1 && pairPos != 1, !(kFbSkip && chain_skips_fb(TA, frame)));
     } else if constexpr ((OPT & OPT_LEAN) != 0 && !accPf) {
 #ifdef IRT_PROBE_BUILD
       if (TA.probeExit == 6) {  // measurement only (probe build): the lerp without its accum read

@@ -229,8 +229,10 @@ int irt_render_tiles(irt_context *ctx, const irt_launch_params *lp, int width, i
  * irt_render_tiles and is what each rank runs in the multi-GPU weak-scaling split.
  * The frames are chained per pixel inside the one launch (frame f's workgroup of a block
  * lerps once frame f - 1's has published the same pixels), so the next frame's workgroups
- * fill the chip while the previous frame's last ones finish; every frame's accum and fb
- * are written, as numFrames separate launches would.
+ * fill the chip while the previous frame's last ones finish.  Every frame's accum is written;
+ * fb is converted and stored by the launch's last frame (earlier frames may skip it) and holds, when the launch ends,
+ * the bytes numFrames separate launches would leave (a pixel whose ray misses the world box in
+ * the last frame: those of its latest earlier hit in the launch; none: untouched).
  * A hand-off wait is bounded (~1 s).  If one ever gives up, the launch's frames were lerped
  * out of order, and the launch fails loudly instead of returning wrong pixels silently: the
  * next call on the context that sees it -- any irt_render* call, irt_get_render_stats*,
