@@ -142,7 +142,7 @@ struct irt_context {
   irt_render_stats total{};
   long long totalLaunches = 0;
   size_t bytes = 0;
-  int variant = irt::kDefaultVariant;  // render-kernel variant (irt_render.hip OPT_* bits)
+  int variant = irt::kDefaultVariant;  // render-kernel variant (irt_kernels.h OPT_* bits)
   // Measured-cost workgroup scheduling of the one-kernel raygen: every launch records its
   // workgroups' durations (d_schedCost); now and then a launch copies them back
   // (h_schedCost, pinned, per launch slot), and once that copy has landed the host

@@ -148,8 +148,72 @@ constexpr int kQueueWords = 9 * kQueueLine;
 // Event counts kept per workgroup: [0] launched [1] inBox [2] locate [3] found [4] candidates
 constexpr int kCnt = 8;
 
-// Render-kernel variants: the bit set of irt_render.hip's OPT_* flags (bits 8-11: minimum
-// waves per SIMD).  All give identical results.
+// Render-kernel variants: a bit set of these OPT_* flags (bits 8-11: minimum waves per SIMD).
+// All give identical results.  (A/B): compiled only into the A/B library, make VARIANTS=all.
+// The switches that were measured, lost and removed are listed in DESIGN.md section 5.
+enum : int {
+  OPT_WEDGE = 16384,  // CUBQL / TRIANGLE samplers (locate_wedge, locate_tri); kept out of
+                      // the default kernels
+  OPT_GRID = 8192,    // GRID_ACCEL_MODE traversal (render_grid); likewise
+  OPT_STATS = 32768,  // per-wave statistics into counters[5..15] (measurement only; with the
+                      // cooperative loop [7] entry hops, [8] locate rounds, [12..15] samples by
+                      // candidates tested 0/1/2/>=3)
+  OPT_SERIAL = 65536, // one lane per ray through the Woodcock loop (render_pixel), for A/B:
+                      // the default user-geometry/sphere kernel is render_pixel_coop
+  OPT_SCAN1 = 131072, // the cooperative loop with each lane's candidate scan on its own
+                      // (locate), for A/B against Tracer::locate_wave
+  OPT_TIMING = 524288,  // measurement only: per-wave shader-clock time by region into
+                        // counters[5..15] (Tracer::tmark)
+  OPT_WAVEWG = 4194304,   // (with OPT_LEAN) one wave per workgroup: a wave's LDS is freed as
+                          // soon as it finishes, instead of when its workgroup's last wave does
+  OPT_LEAN = 2097152,   // less LDS per workgroup (31.0 -> 24 KB), so that more workgroups
+                        // fit a CU while finished waves wait for their workgroup's last one:
+                        // the sRGB thresholds and the sphere hash read from global memory
+                        // (L1/L2), the accum pixel loaded at the end instead of prefetched
+  OPT_QUEUE = 16777216,  // the persistent launch (RenderArgs::queue): every resident wave pulls
+                        // 8x8-pixel packets from the launch's counter; its own instantiation
+                        // of the default kernel (k_render's grid launch is unchanged)
+  OPT_FASTSPH = 33554432,  // (A/B) the sdda entry/exit cells from the certified fast lat/lon
+                           // (irt_device.h spherical_fast, glibc-exact fallback near cell edges):
+                           // no gain at C3, C5 3 % slower (profiles/r04b/) -- the setup waits on
+                           // the majorant gather, not on asinf/atan2f
+  OPT_SPLIT = 8,  // measured-cost work items (RenderArgs::splitList): the launches of a single frame
+                  // that split packets run this instantiation of the default kernels (kernel_for)
+  OPT_DPPSCAN = 32,  // groups of 2, 4, 16 and 64 lanes take the round's prefix t0 - d0 - ... - dk
+                     // by DPP steps across lanes (woodcock_wave), not each lane from LDS
+  OPT_DMATAB = 67108864,  // one-wave workgroups: the LCG jump and logf tables loaded into
+                          // LDS by LDS-DMA, not waited for in the prologue (k_render)
+  OPT_NOMISS = 262144,  // the user-geometry cooperative loop without its miss mode:
+                        // every sample outside all cells ends its ray's round (round 4's
+                        // default); convert_icon terrain leaves voids under land, where such runs
+                        // cost one round per miss
+  OPT_VOIDLOC = 1073741824,  // the solo lanes' void walk also in located mode: a certain miss at
+                             // the round's sample switches the ray to miss mode there, not a round
+                             // later; scenes with holes run it since round 6 (scene_variant:
+                             // profiles/r06zg/ C3t chained -1.7 %, single frames even)
+  OPT_NOVOIDRUN = 2,   // (A/B) the miss-mode kernels without the solo lanes' void walk (woodcock_wave)
+  OPT_NOHOLESKIP = 4,  // (A/B) the miss-mode kernels without the quad-bound miss test (Tracer::locate_wave:
+                       // a sample outside its quad's radial range is outside every cell, no
+                       // candidate tested)
+  OPT_SLOT = 128,  // the wave-wide scan starts from the slot table (RenderArgs::slots, irt_common.h
+                   // kSlot4): the first admitted candidate and the list's position in one gather,
+                   // instead of the header, then the entry; launches on a scene with a table run
+                   // this instantiation of the default kernels (kernel_for)
+  // bits 8-11: minimum waves per SIMD asked of the register allocator (0: none)
+};
+// OPT_MONO is kept in the numbering of round 1 (the one-kernel raygen; the setup -> march ->
+// continuation pipeline it distinguished from was removed): every listed variant sets it, and
+// kernel_for masks it off.
+// 5376 (the default until round 4): four-wave workgroups at 5 waves/SIMD, 96 VGPRs, the few spills
+// in the prologue and epilogue only; 5120: the same kernel at 4 waves/SIMD (117 VGPRs).  70656 =
+// 5120 | OPT_SERIAL: the one-lane-per-ray Woodcock loop, against the cooperative loop.  2102272 =
+// 5120 | OPT_LEAN (24 KB of LDS per workgroup), 2102528 the same at 5 waves/SIMD; 6296576 /
+// 6296832 = 2102272 / 2102528 | OPT_WAVEWG (one-wave workgroups); 73405696 = 6296832 | OPT_DMATAB,
+// 73405728 = 73405696 | OPT_DPPSCAN (the default since round 5), 73667872 its hole-free form (|
+// OPT_NOMISS), 1147147552 its form for scenes with holes (| OPT_VOIDLOC).  73930016 / 74192160: the
+// default / its hole-free form with OPT_TIMING (per-region shader clocks, profiles/probe.py;
+// s_memtime slows them ~17x).
+constexpr int OPT_MONO = 4096;
 // one kernel per frame, 5 waves/SIMD (96 VGPRs; spills only in the prologue/epilogue): against
 // 4 waves C3 -1.8 %, C4 -4.9 %, comb TF -9 %, C5 +1.9 % (profiles/r03u_waves/)
 // Round 4: one-wave workgroups with the leaner LDS (OPT_WAVEWG | OPT_LEAN, 5 waves/SIMD): a
@@ -165,7 +229,7 @@ constexpr int kDefaultVariant = 73405728;
 // without holes (every column starting at the same radius, no gaps inside columns) runs it
 // without (bit 262144, OPT_NOMISS): C3 -2.3 %, while convert_icon terrain (voids under land)
 // runs 2.25x faster with it (profiles/r05d/)
-constexpr int kNoMissBit = 262144;
+constexpr int kNoMissBit = OPT_NOMISS;
 // measured-cost scheduling (irt_context.hip sched_prepare): at most this many work items run first
 // in a single frame (RenderArgs::splitList), a multiple of 8
 constexpr uint32_t kMaxSplit = 4096;
@@ -173,15 +237,16 @@ constexpr uint32_t kMaxSplit = 4096;
 // OPT_VOIDLOC: a solo lane whose sample is outside its quad's records switches its ray to the miss
 // mode in the same round and walks on): C3t 8 chained frames -1.7 %, one per launch even
 // (profiles/r06zg/)
-constexpr int kVoidLocBit = 1073741824;
+constexpr int kVoidLocBit = OPT_VOIDLOC;
+// The Tracer instantiation kernel_for picks for the unstructured samplers' sphere-accel launches
+// (256-thread workgroups, full LDS, no waves-per-SIMD floor), which k_debug_locate_sampler runs too
+constexpr int kSamplerVariant = ((kDefaultVariant & ~OPT_MONO) & ~(0xF00 | OPT_WAVEWG | OPT_LEAN)) | OPT_WEDGE;
 inline int scene_variant(bool holes) { return holes ? kDefaultVariant | kVoidLocBit : kDefaultVariant | kNoMissBit; }
 bool render_variant_available(int variant);
 int render_variants(int *out, int cap);  // the compiled variants (count; the first cap into out)
 // workgroups per 256-pixel block the launch of `variant` uses for these arguments (4 only for
 // the one-wave-workgroup A/B variants on the user-geometry sphere path)
 int render_wg_per_block(const RenderArgs &A, int variant);
-// chained frames per wave (2: the OPT_FPAIR variants, irt_render.hip)
-int render_frames_per_wave(const RenderArgs &A, int variant);
 // whether `variant` can run as a persistent launch (RenderArgs::queue) with these arguments:
 // the cooperative user-geometry sphere-accel kernels with 256-thread workgroups
 bool render_queue_ok(const RenderArgs &A, int variant);

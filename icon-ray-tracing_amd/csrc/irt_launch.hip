@@ -293,10 +293,10 @@ bool whole_kernel(const irt_context *c) { return c->probeExit == 0 || c->probeEx
 // Frames of one launch can be chained: the cooperative kernels (not the one-lane-per-ray A/B
 // variant), grid launches (`queue`: a persistent one), no measurement-only early exit
 bool chain_capable(const irt_context *c, bool queue) {
-  return c->chainOn && !queue && whole_kernel(c) && (c->variant & 65536) == 0;
+  return c->chainOn && !queue && whole_kernel(c) && (c->variant & OPT_SERIAL) == 0;
 }
 
-bool stats_variant(const irt_context *c) { return (c->variant & (32768 | 524288)) != 0; }  // statistics, timing
+bool stats_variant(const irt_context *c) { return (c->variant & (OPT_STATS | OPT_TIMING)) != 0; }  // statistics, timing
 
 int validate(const irt_context *c, const irt_launch_params *lp, const RenderRequest &r, const uint32_t *fb,
              const irt_vec4f *accum) {
@@ -493,8 +493,8 @@ int decide_sched(irt_context *c, const irt_launch_params *lp, const RenderReques
 }
 
 // Whether the frames are chained, and the workgroups of this launch: 16 per 64x64 tile, x4 for
-// the one-wave-workgroup variants (irt_render.hip OPT_WAVEWG, bit 4194304), per frame (per pair of
-// frames), + the split packets' parts; a persistent launch's resident ones
+// the one-wave-workgroup variants (OPT_WAVEWG), per frame, + the split packets' parts; a
+// persistent launch's resident ones
 void count_workgroups(const irt_context *c, const RenderRequest &r, Launch &L) {
   RenderArgs &A = L.A;
   // The hand-off's buffer resources address accum with 32-bit byte offsets: frames of 2^27
@@ -503,11 +503,8 @@ void count_workgroups(const irt_context *c, const RenderRequest &r, Launch &L) {
   // (decided from whether this launch is in fact queued: see render_sequence)
   A.chain = r.numFrames > 1 && chain_capable(c, L.queued) && outPixels * 16u <= 0x7FFFFFFFull ? 1 : 0;
   A.numSamples = r.numFrames;
-  // two chained frames per wave (the OPT_FPAIR variants, bit 1): half the grid's frame rows
-  const int fpw = render_frames_per_wave(A, c->variant);
   L.numWG = L.queued ? (size_t)L.queueWG
-                     : (size_t)L.numTiles * 16 * (size_t)render_wg_per_block(A, c->variant) *
-                               (size_t)((r.numFrames + fpw - 1) / fpw) +
+                     : (size_t)L.numTiles * 16 * (size_t)render_wg_per_block(A, c->variant) * (size_t)r.numFrames +
                            (size_t)A.numSplit;
 }
 

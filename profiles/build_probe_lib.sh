@@ -11,5 +11,5 @@ mkdir -p $P/build-x5
   -mllvm -amdgpu-load-store-vectorizer=0 -DIRT_ALL_VARIANTS -DIRT_PROBE_BUILD -c $P/csrc/irt_render.hip -o $P/build-x5/irt_render.o
 B=$P/build-all
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $P/libicon_rt_hip_probe.so $B/irt_host.o $B/irt_scene.o \
-  $B/irt_synth.o $B/irt_debug.o $B/irt_netcdf.o $B/irt_convert.o $B/irt_kernels.o $P/build-x5/irt_render.o \
-  $B/irt_context.o $B/irt_build.o -lpthread
+  $B/irt_synth.o $B/irt_debug.o $B/irt_netcdf.o $B/irt_convert.o $B/irt_sched.o $B/irt_kernels.o $P/build-x5/irt_render.o \
+  $B/irt_context.o $B/irt_launch.o $B/irt_debug_hooks.o $B/irt_build.o -lpthread
