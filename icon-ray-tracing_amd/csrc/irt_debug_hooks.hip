@@ -315,6 +315,8 @@ extern "C" int irt_debug_slot_use(const irt_context *c, double *tfSamples) {
   return c->slot.slots && (c->slotAlways || c->slotSparse) ? 1 : 0;
 }
 
+extern "C" long long irt_debug_void_use(const irt_context *c) { return c ? c->lastVoid : -1; }
+
 extern "C" int irt_debug_context_array(const irt_context *c, int which, void *dst, size_t capacity,
                                        size_t *bytes) {
   if (!c || !bytes || c->building) {

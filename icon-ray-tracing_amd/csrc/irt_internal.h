@@ -131,6 +131,55 @@ uint32_t sched_order(const uint32_t *cost, int numBlocks, int tilesX, int tileSt
                      int splitLg, float splitFactor, int numCU, bool wavewg, size_t cap,
                      uint32_t maxSplit, uint32_t *out);
 
+// Void packets (host/irt_void.cpp): the 8x8 packets of a launch all of whose rays, whatever the
+// jitter, pass boxTest and miss the shell's outer sphere -- colour zero in every frame.  Bit
+// 4 * block + wave of the launch's blocks (16 per launch tile k: frame tile tileList[k], or
+// tileBegin + k * tileStride), as the chain's publish words are indexed; a packet's inactive pixels
+// (x >= W or y >= H) are not looked at, one without active pixels is never flagged.  Nothing is
+// flagged for another raygen, accel mode or sampler, or for a camera the float error bound does not
+// cover (see the file's head).  Every member is 4 bytes wide and the pointer comes last: no padding,
+// so a request compares bytewise.
+struct VoidRequest {
+  float cam[12];  // org, dir_00, dir_du, dir_dv
+  float bmin[3], bmax[3];
+  float rOuter, rInner;
+  int W, H, tileBegin, tileStride, numTiles;
+  int raygen, accelMode, mode;
+  const int32_t *tileList;  // numTiles ids, or null
+};
+// the request of a launch with these parameters over a scene with these facts
+inline VoidRequest void_request(const irt_launch_params &lp, const irt_volume_info &info, int W, int H, int tileBegin,
+                                int tileStride, int numTiles, const int32_t *tileList) {
+  VoidRequest q;
+  const irt_vec3f *cam[4] = {&lp.org, &lp.dir_00, &lp.dir_du, &lp.dir_dv};
+  for (int k = 0; k < 4; ++k) {
+    q.cam[3 * k] = cam[k]->x;
+    q.cam[3 * k + 1] = cam[k]->y;
+    q.cam[3 * k + 2] = cam[k]->z;
+  }
+  q.bmin[0] = info.bounds.lower.x, q.bmin[1] = info.bounds.lower.y, q.bmin[2] = info.bounds.lower.z;
+  q.bmax[0] = info.bounds.upper.x, q.bmax[1] = info.bounds.upper.y, q.bmax[2] = info.bounds.upper.z;
+  q.rOuter = info.sphericalBounds.upper.x;
+  q.rInner = info.sphericalBounds.lower.x;
+  q.W = W, q.H = H, q.tileBegin = tileBegin, q.tileStride = tileStride, q.numTiles = numTiles;
+  q.raygen = lp.raygen, q.accelMode = lp.accelMode, q.mode = lp.mode;
+  q.tileList = tileList;
+  return q;
+}
+inline size_t void_words(int numTiles) { return ((size_t)(numTiles > 0 ? numTiles : 0) * 64 + 31) / 32; }
+// bits: void_words(numTiles) words; returns the number of packets flagged
+uint32_t void_packets(const VoidRequest &q, uint32_t *bits);
+// ... and the last request's bitmap, kept while the request stays the same (tile lists by content)
+struct VoidCache {
+  std::vector<unsigned char> key;
+  std::vector<uint32_t> bits;
+  uint32_t count = 0;                   // packets flagged (0 while the bitmap is not computed)
+  bool keyed = false, valid = false;    // a request was seen; its bitmap is computed
+  long long generation = 0;             // bitmaps computed so far
+  // true: computed anew.  defer: a new request is only noted, and computed when it comes again
+  bool lookup(const VoidRequest &q, bool defer = false);
+};
+
 // Synthetic RnBk grid generator (host/irt_synth.cpp): open once, fill any record range.
 int synth_open(int rootN, int bisections, int levels, float topHeight, float noise, uint32_t seed,
                float terrainHeight,

@@ -137,6 +137,13 @@ struct RenderArgs {
   float slotEdge[3];
   int slotBins;
   int slotSubs;
+  // Void packets of a chained launch of progressive frames of one camera (host/irt_void.cpp; null:
+  // not in use): bit 4 block + wave set = every ray of that packet, whatever the jitter, passes
+  // boxTest and misses the outer sphere, so each frame only scales the pixel: nv = w_f 0 + (1 - w_f)
+  // old.  Frame 0's wave of such a packet applies all numSamples lerps in order and stores accum
+  // and fb once (irt_raygen.h void_packet); the later frames' waves return at once -- no hand-off, their
+  // publish words keep an earlier launch's epoch, which nothing waits for.
+  const uint32_t *voidBits;
 };
 // a persistent launch's queue words (irt_render.hip queue_take): 8 per-XCD counters and the
 // done count, each on its own 128-B line
@@ -199,6 +206,9 @@ enum : int {
                    // kSlot4): the first admitted candidate and the list's position in one gather,
                    // instead of the header, then the entry; launches on a scene with a table run
                    // this instantiation of the default kernels (kernel_for)
+  OPT_VOID = 16,  // the default kernels' form for chained launches that carry a void-packet bitmap
+                  // (RenderArgs::voidBits; kernel_for): the packet's bit is tested at the kernel's top.
+                  // Every other launch runs the kernels without the test, as before
   // bits 8-11: minimum waves per SIMD asked of the register allocator (0: none)
 };
 // OPT_MONO is kept in the numbering of round 1 (the one-kernel raygen; the setup -> march ->
@@ -254,6 +264,9 @@ bool render_queue_compiled();  // the A/B library (make VARIANTS=all) only
 // whether a single frame of `variant` can run measured-cost work items (RenderArgs::splitList):
 // the default kernels with one-wave workgroups
 bool render_split_ok(const RenderArgs &A, int variant);
+// whether a chained launch of `variant` with these arguments can merge its void packets
+// (RenderArgs::voidBits): the default kernels with one-wave workgroups, without the slot table
+bool render_void_ok(const RenderArgs &A, int variant);
 // workgroups a persistent launch of `variant` runs on a device with numCU compute units:
 // every slot the kernel's occupancy allows (resident at once), at most `numBlocks`
 int render_queue_wgs(const RenderArgs &A, int variant, int numCU, int numBlocks);

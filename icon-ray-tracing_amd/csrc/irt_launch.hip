@@ -580,6 +580,49 @@ int setup_chain(irt_context *c, int numFrames, Launch &L) {
   return IRT_OK;
 }
 
+// Void packets (RenderArgs::voidBits, host/irt_void.cpp): chained progressive frames of one camera
+// render the packets that can only ever give the zero colour once per launch.  Only launches that
+// can use the bitmap compute it -- several chained frames of one camera through the default
+// kernels (render_void_ok), the raygen over the shell's spheres; not with the chain test hook set
+// (its withheld frame must stall every packet), a measurement-only exit or the statistics and
+// timing variants (their per-wave figures) -- and the cache computes it only when the same request
+// comes a second time (VoidCache::lookup, defer): a progressive sequence once, at its second
+// launch (0.4 ms of host time at 1024^2, 0.8 ms at 2048^2 -- DESIGN.md section 5.1 -- against 0.02
+// and 0.1 ms saved per launch of 8 frames); a camera that gets one launch, and a new camera with
+// single-frame launches, never.  The device copy is one buffer, as d_frameCams and d_chainFlag are:
+// it is rewritten on the launching stream when the cache has computed a new bitmap, which is behind
+// every launch that reads the old one only because a context's launches run in call order, also
+// across streams (claim_slot); the upload goes through this launch slot's pinned staging.
+int prepare_void(irt_context *c, const irt_launch_params *lp, const RenderRequest &r, Launch &L) {
+  RenderArgs &A = L.A;
+  c->lastVoid = 0;
+  if (!(A.chain && !r.seq && r.numFrames > 1 && L.numTiles > 0 && c->chainWithhold < 0 && c->probeExit == 0 &&
+        !stats_variant(c) && lp->raygen == IRT_RAYGEN_WITH_ACCEL && lp->accelMode == IRT_ACCEL_SPHERE &&
+        render_void_ok(A, c->variant)))
+    return IRT_OK;
+  c->voidCache.lookup(void_request(*lp, c->info, r.W, r.H, r.tileBegin, r.tileStride, L.numTiles, r.tileList), true);
+  if (!c->voidCache.count) return IRT_OK;
+  const size_t words = void_words(L.numTiles);
+  if (words > c->voidCap) {
+    // every launch that may still read the old words, on any stream, and every slot's staging
+    int rc = grow(c, Retire::SlotsThenStream, L.s, &c->voidCap, words,
+                  {{(void **)&c->d_voidBits, [](size_t n) { return n * sizeof(uint32_t); }, false},
+                   {(void **)&c->h_voidBits, [](size_t n) { return kSlots * n * sizeof(uint32_t); }, true}},
+                  nullptr);
+    c->voidOnDevice = 0;
+    if (rc) return rc;
+  }
+  if (c->voidOnDevice != c->voidCache.generation) {
+    uint32_t *h = c->h_voidBits + (size_t)L.slot * c->voidCap;
+    memcpy(h, c->voidCache.bits.data(), words * sizeof(uint32_t));
+    IRT_HIP(hipMemcpyAsync(c->d_voidBits, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, L.s));
+    c->voidOnDevice = c->voidCache.generation;
+  }
+  A.voidBits = c->d_voidBits;
+  c->lastVoid = c->voidCache.count;
+  return IRT_OK;
+}
+
 // a sequence of views (irt_render_sequence): frame k's camera and accumID as 4 float4
 int stage_sequence(irt_context *c, const RenderRequest &r, Launch &L) {
   RenderArgs &A = L.A;
@@ -686,7 +729,8 @@ int render_impl(irt_context *c, const irt_launch_params *lp, const RenderRequest
   decide_queue(c, r.numFrames, L);
   if ((rc = decide_sched(c, lp, r, L))) return rc;
   count_workgroups(c, r, L);
-  if ((rc = choose_counters(c, L)) || (rc = setup_chain(c, r.numFrames, L)) || (rc = stage_sequence(c, r, L)) ||
+  if ((rc = choose_counters(c, L)) || (rc = setup_chain(c, r.numFrames, L)) || (rc = prepare_void(c, lp, r, L)) ||
+      (rc = stage_sequence(c, r, L)) ||
       (rc = ensure_samples(c, r.numFrames, L)))
     return rc;
   return launch_and_commit(c, L);

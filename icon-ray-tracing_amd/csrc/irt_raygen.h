@@ -261,6 +261,55 @@ __device__ __forceinline__ void flush_counters(const RenderArgs &A, const uint32
   }
 }
 
+// A void packet of a chained launch (RenderArgs::voidBits): in every frame each of its rays passes
+// boxTest and misses both spheres -- numRanges == 0, colour (0, 0, 0, 0) -- so frame g only lerps
+// the zero colour into the pixel.  Frame 0's wave does that for every frame of the launch, in frame
+// order and with write_pixel_chain's expressions (the products and sums stay: w * 0 + -0 is +0, and
+// NaN or inf in accum go through as they would), then stores accum and the RGBA8 of the final value
+// once, with the streaming stores the launch's last frame uses; the later frames' waves do nothing.
+// The wave's counts are those of its frames' waves (rays launched = rays in the box = active
+// pixels), stored or added as flush_counters does; no LDS, no wait, no publish.
+__device__ __forceinline__ void void_packet(const RenderArgs &KA, uint32_t blk, int pwave, int frame) {
+  // the launch's arguments through a per-lane pointer, as chain_replay_fb reads them: vector loads
+  // into VGPRs, all free here, and none of the raygen's scarce SGPRs
+  const RenderArgs *vp = &KA;
+  asm volatile("" : "+v"(vp));
+  const RenderArgs &A = *vp;
+  const int lane = (int)__lane_id();
+  const Pixel px = pixel_of(A, blk, pwave * 64 + lane);
+  if (frame == 0 && px.active) {
+    float4 nv = A.accum[px.outIdx];
+    const float c = 0.f;
+#pragma nounroll
+    for (int g = 0; g < A.numSamples; ++g) {
+      const float w = 1.f / (float)(A.accumID + g + 1);
+      nv.x = w * c + (1.f - w) * nv.x;
+      nv.y = w * c + (1.f - w) * nv.y;
+      nv.z = w * c + (1.f - w) * nv.z;
+      nv.w = w * c + (1.f - w) * nv.w;
+    }
+    const float *th = A.srgbTh;
+    const uint32_t rgba = srgb_byte(th, nv.x) + (srgb_byte(th, nv.y) << 8) + (srgb_byte(th, nv.z) << 16) +
+                          (make_8bit(nv.w) << 24);
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    const f4v t = {nv.x, nv.y, nv.z, nv.w};
+    __builtin_nontemporal_store(t, reinterpret_cast<f4v *>(&A.accum[px.outIdx]));
+    __builtin_nontemporal_store(rgba, &A.fb[px.outIdx]);
+  }
+  if (A.counters) {
+    const uint32_t n = (uint32_t)__popcll(__ballot(px.active));
+    const size_t wg = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (A.wgCounts) {
+      if (lane < kCnt) A.wgCounts[wg * kCnt + lane] = lane < 2 ? n : 0u;
+    } else if (lane < 2 && n) {
+      unsigned long long *dst = A.counterBuckets ? A.counterBuckets + (wg % kCounterBuckets) * 8 : A.counters;
+      atomicAdd(&dst[lane], (unsigned long long)n);
+    }
+  }
+  if (A.wgTrace && lane == 0)  // measurement only
+    A.wgTrace[4 * (blockIdx.y * gridDim.x + blockIdx.x) + 1] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+}
+
 // sample-buffer marker of a frame whose ray missed the box (alpha is 0 or 1 otherwise)
 constexpr float kNoSample = -1.f;
 

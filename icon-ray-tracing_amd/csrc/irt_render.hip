@@ -99,6 +99,26 @@ __global__ void __launch_bounds__((OPT & OPT_WAVEWG) ? 64 : 256,
     w[3] = __builtin_amdgcn_s_getreg((15 << 11) | 20);  // HW_REG_XCC_ID
   }
   if (A.probeExit == 1) return;  // measurement only
+  // Void packets (OPT_VOID: the kernels of launches with A.voidBits -- chained progressive frames of
+  // one camera; irt_launch.hip prepare_void, kernel_for): the packet's bit, by the scalar unit,
+  // before anything else is in flight -- the prologue's LDS-DMA included.  Such a launch has no
+  // block order and no split items, so the workgroup's packet is the one the grid deal below gives it.
+  constexpr bool kVoid = (OPT & OPT_VOID) != 0;
+  static_assert(!kVoid || (wavewg && lean && Tracer<OPT>::kCoop &&
+                           (OPT & (OPT_SPLIT | OPT_SLOT | OPT_STATS | OPT_TIMING | OPT_QUEUE | OPT_GRID | OPT_WEDGE)) == 0),
+                "void packets: the default kernels' plain grid form");
+  if constexpr (kVoid) {
+    // (the arguments through fresh_args(): nothing this test loads stays live into the raygen)
+    const RenderArgs &VA = fresh_args();
+    const uint32_t vb = blockIdx.x, vwave = (vb >> 3) & 3u;
+    const uint32_t vblk = ((vb >> 5) << 3) | (vb & 7u), vpkt = vblk * 4u + vwave;
+    uint32_t isVoid = VA.voidBits ? (scalar_word(VA.voidBits, vpkt >> 5) >> (vpkt & 31u)) & 1u : 0u;
+    asm volatile("" : "+s"(isVoid));  // one opaque scalar branch: the raygen below compiles as without it
+    if (isVoid) {
+      void_packet(VA, vblk, (int)vwave, (int)blockIdx.y);
+      return;
+    }
+  }
   uint64_t tStart = 0;
   if constexpr ((OPT & OPT_TIMING) != 0) tStart = __builtin_amdgcn_s_memtime();
   // OPT_DMATAB (one-wave workgroups): the LCG jump and logf tables go straight from global
@@ -539,6 +559,11 @@ bool render_split_ok(const RenderArgs &A, int variant) {
          render_wg_per_block(A, variant) == 4;
 }
 
+// (kernel_for then picks the OPT_VOID form, which has no OPT_SLOT or OPT_SPLIT sibling)
+bool render_void_ok(const RenderArgs &A, int variant) {
+  return render_split_ok(A, variant) && !A.slots && !A.queue && !A.numSplit && !A.schedOrder;
+}
+
 bool render_queue_compiled() {
 #ifdef IRT_ALL_VARIANTS
   return true;
@@ -580,6 +605,8 @@ RenderKernel kernel_for(const RenderArgs &A, int &threads) {
   // and a scene with a slot table: their OPT_SLOT form
   if constexpr (K == (kDefaultVariant & ~OPT_MONO) || K == ((kDefaultVariant | kNoMissBit) & ~OPT_MONO) ||
                 K == ((kDefaultVariant | OPT_VOIDLOC) & ~OPT_MONO)) {
+    // chained progressive frames with a void-packet bitmap (render_void_ok: no table, no split items)
+    if (A.voidBits) return k_render<K | OPT_VOID>;
     if (A.slots) return A.numSplit ? k_render<K | OPT_SPLIT | OPT_SLOT> : k_render<K | OPT_SLOT>;
     if (A.numSplit) return k_render<K | OPT_SPLIT>;
   }
@@ -647,6 +674,10 @@ void prewarm_variant(hipStream_t s) {
   const RenderKernel kt = kernel_for<N>(A, threads);
   if (kt != k) hipLaunchKernelGGL(kt, dim3(1), dim3(threads), 0, s, A);
   A.slots = nullptr;
+  A.voidBits = reinterpret_cast<const uint32_t *>(16);  // the void-packet form (never dereferenced)
+  const RenderKernel kv = kernel_for<N>(A, threads);
+  if (kv != k) hipLaunchKernelGGL(kv, dim3(1), dim3(threads), 0, s, A);
+  A.voidBits = nullptr;
   A.queue = reinterpret_cast<uint32_t *>(16);  // never dereferenced: the kernel returns first
   const RenderKernel kq = kernel_for<N>(A, threads);
   if (kq != kernel_for<N>(RenderArgs{}, threads)) hipLaunchKernelGGL(kq, dim3(1), dim3(256), 0, s, A);

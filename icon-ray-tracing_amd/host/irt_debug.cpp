@@ -15,6 +15,10 @@ struct irt_debug_scene {
   WedgeScene w;
 };
 
+struct irt_debug_void_cache {
+  VoidCache c;
+};
+
 extern "C" {
 
 float irt_debug_asinf(float x) { return glibc_asinf(x); }
@@ -203,6 +207,37 @@ int irt_debug_sched_order(const uint32_t *cost, int numBlocks, int tilesX, int t
   }
   *numSplit = sched_order(cost, numBlocks, tilesX, tileStride, policy, splitLg, splitFactor, numCU,
                           wavewg != 0, capacity, maxSplit, out);
+  return IRT_OK;
+}
+
+irt_debug_void_cache *irt_debug_void_cache_create(void) { return new irt_debug_void_cache(); }
+void irt_debug_void_cache_free(irt_debug_void_cache *cache) { delete cache; }
+
+int irt_debug_void_packets(irt_debug_void_cache *cache, const irt_launch_params *lp, const irt_volume_info *info,
+                           int W, int H, int tileBegin, int tileStride, const int32_t *tileList, int listCount,
+                           uint32_t *bits, size_t capacity, uint32_t *numVoid, long long *computations) {
+  if (!lp || !info || !numVoid || W <= 0 || H <= 0 || tileBegin < 0 || tileStride <= 0 || listCount < 0) {
+    set_error("irt_debug_void_packets: bad argument");
+    return IRT_E_INVALID;
+  }
+  const int total = ((W + 63) / 64) * ((H + 63) / 64);
+  const int numTiles = tileList ? listCount : tileBegin < total ? (total - tileBegin + tileStride - 1) / tileStride : 0;
+  for (int k = 0; tileList && k < listCount; ++k)
+    if (tileList[k] < 0 || tileList[k] >= total) {
+      set_error("irt_debug_void_packets: tile id %d at %d outside [0, %d)", tileList[k], k, total);
+      return IRT_E_INVALID;
+    }
+  if (void_words(numTiles) > capacity || (!bits && capacity)) {
+    set_error("irt_debug_void_packets: %zu words needed", void_words(numTiles));
+    return IRT_E_INVALID;
+  }
+  const VoidRequest q = void_request(*lp, *info, W, H, tileBegin, tileStride, numTiles, tileList);
+  VoidCache local;
+  VoidCache &vc = cache ? cache->c : local;
+  vc.lookup(q);
+  if (void_words(numTiles)) memcpy(bits, vc.bits.data(), void_words(numTiles) * sizeof(uint32_t));
+  *numVoid = vc.count;
+  if (computations) *computations = vc.generation;
   return IRT_OK;
 }
 

@@ -1,0 +1,237 @@
+// irt_void.cpp -- void packets, the pure part: which 8x8 packets of a launch can only ever render
+// the zero colour (csrc/irt_launch.hip prepare_void caches and uploads the bitmap; k_render reads it).
+//
+// A packet is void when every ray the raygen can generate for its active pixels -- any jitter in
+// [0, 1)^2, in any frame -- passes boxTest and fails intersectSphere on the shell's outer sphere
+// (and so on the inner one): numRanges == 0, no sample, colour (0, 0, 0, 0)
+// (deviceCode.cu:288-340).  That depends on the camera, the frame size, the box and the radii only.
+//
+// The certificate is computed in double and must hold for the FLOAT evaluation of generateRay,
+// boxTest and intersectSphere, as the kernel and the reference run them.  u = 2^-24.
+//
+// 1. The direction.  generateRay evaluates d = (dir_00 + a dir_du) + b dir_dv with a = (x + .5f) +
+//    ju, b = (y + .5f) + jv, each operation rounded: per component at most 8 u (|dir_00| + a |dir_du|
+//    + b |dir_dv|) from the exact value for the exact (a, b) in the CLOSED rectangle [x + .5, x + 1.5]
+//    x [y + .5, y + 1.5] (the rounding of a and b included, and a sum that rounds up to x + 1.5).
+//    With M the sum of those magnitudes over the three components and dmin a lower bound of |d| over
+//    the packet, that turns the direction by at most 8 u M / dmin.  normalize() rounds three
+//    quotients (< 4 u more), and the clamp `fabsf(c) < 1e-5f -> c = 1e-5f` moves each component of
+//    the unit vector by at most 2e-5: sqrt(3) 2e-5 < 3.5e-5.  So the ray the kernel tests deviates
+//    from the exact direction of its (a, b) by at most
+//        delta = 8 u M / dmin + 4e-5 rad,
+//    and its length D satisfies |D - 1| < 1e-4.
+//
+// 2. The sphere.  For the float direction d' (length D) and eye O (length P), intersectSphere
+//    computes disc = B B - 4 A C with A = d'.d', B = 2 d'.O, C = O.O - R R.  Exactly,
+//    disc = 4 D^2 (R^2 - p^2), p the distance of the line from the centre = P sin(theta), theta the
+//    angle between d' and -O.  The float errors: B/2 is off by <= 3.1 u D P, so B B by <= 29 u D^2
+//    P^2; C by <= 5.1 u P^2 and A by 3.1 u D^2, so 4 A C by <= 37 u D^2 P^2; the last subtraction by
+//    <= 8 u D^2 P^2: |error| <= 74 u D^2 P^2 < 4 D^2 P^2 eps with eps = 32 u = 2^-19.  The float
+//    disc is negative -- the test fails, as required -- whenever
+//        sin^2(theta) > (R / P)^2 + eps.
+//    This first-order bound is used only while eps P^2 <= R^2 / 100 (P < 72 R; an eye farther away
+//    classifies nothing) and for P > 1.001 R (an eye inside or on the sphere classifies nothing).
+//    The directions that miss a sphere are not convex, so the packet is bounded by its centre
+//    direction and the largest angle `ext` from it to a corner of its rectangle (the angle to a
+//    fixed direction is quasi-convex on the image plane below 90 degrees, so its maximum over a
+//    rectangle is at a corner): every tested ray has theta in [tc - ext - delta, tc + ext + delta],
+//    sin^2 is smallest at the ends of an interval inside [0, pi], and both ends are checked -- on
+//    cosines, with ext bounded from the image plane (sphere_rect: no inverse trigonometry).  Where
+//    one cone around the whole rectangle is too coarse, the same test on each quarter of it
+//    (recursively, to 64 pieces) covers the rectangle piece by piece.  A 64x64 tile is tried as
+//    one rectangle first: most tiles lie wholly off the globe or wholly on it.
+//    The inner sphere: r <= R makes its float C no smaller and its float disc no larger (every
+//    operation is monotone under rounding), so it fails whenever the outer one does.
+//
+// 3. The box.  The directions from the eye that hit a convex body form a convex cone, so if the four
+//    corner directions of the packet's rectangle hit the box shrunk by s on every side, every exact
+//    direction of the packet passes through a point q of the shrunk box, at a distance of at most T
+//    (the farthest box corner from the eye).  The tested ray, turned by at most delta, passes within
+//    T delta of q: through a point at least c = s - T delta inside every face, so its exact slab
+//    interval has t1 - t0 >= 2 c / D and t1 > 0.  boxTest's quotients (a correctly rounded
+//    difference, a correctly rounded quotient; the clamp keeps every divisor nonzero) are each within
+//    2.1 u of exact, signs kept, so the float test passes when 2 c / D > 2.2 * 2.1 u * T / D; c >= 3e-7 T
+//    covers it.  Hence s = T (delta + 4e-7), and T < 1e9 keeps the ray's tmax = 1e10 out of it.
+//
+// A camera any of this cannot cover (non-finite words, du/dv that let |d| vanish over a packet, a
+// box thinner than 2 s) classifies nothing.
+
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "irt_internal.h"
+
+namespace irt {
+
+namespace {
+
+struct V3 {
+  double x, y, z;
+};
+V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+V3 operator*(double s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
+double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+double norm(V3 a) { return sqrt(dot(a, a)); }
+double abs1(V3 a) { return fabs(a.x) + fabs(a.y) + fabs(a.z); }
+
+// the exact slab test of the ray org + t d, t > 0, against [lo, hi]
+bool hits_box(V3 org, V3 d, const double lo[3], const double hi[3]) {
+  const double o[3] = {org.x, org.y, org.z}, dd[3] = {d.x, d.y, d.z};
+  double t0 = 0.0, t1 = INFINITY;
+  for (int k = 0; k < 3; ++k) {
+    if (dd[k] == 0.0) {
+      if (!(o[k] > lo[k] && o[k] < hi[k])) return false;
+      continue;
+    }
+    const double a = (lo[k] - o[k]) / dd[k], b = (hi[k] - o[k]) / dd[k];
+    t0 = std::max(t0, std::min(a, b));
+    t1 = std::min(t1, std::max(a, b));
+  }
+  return t0 < t1;
+}
+
+// The camera and what the sphere test needs of it, once per request
+struct View {
+  V3 org, d00, du, dv, axis;
+  double uu, vv, uv;     // du.du, dv.dv, |du.dv|
+  double m0, mu, mv;     // the 1-norms of d00, du, dv (M of the head's section 1)
+  double cosN, sinN;     // of `need`, the angle every tested ray must keep from the axis
+  V3 dir(double a, double b) const { return d00 + a * du + b * dv; }
+};
+struct Rect {
+  double a0, a1, b0, b1;  // screen coordinates, closed
+};
+enum { kUnbounded = -2, kCentreHits = -1, kUndecided = 0, kClear = 1, kAllHit = 2 };
+
+// One rectangle against the sphere, without inverse trigonometry.  c its centre direction, h the
+// largest image-plane distance from the centre to a corner, dmin = |c| - h <= |d| over it: every
+// exact direction is within x0 = 1.01 h / dmin of c (sin(angle) <= h / dmin < 0.2, and asin(t) <
+// 1.01 t there), every tested ray within x = x0 + delta.  With ct = cos(angle of c to the axis):
+//   theta_c - x > need        <=  ct < cos(need + x),  and cos(need + x) >= cosN (1 - x^2/2) - sinN x;
+//   theta_c + x < pi - need   <=  ct > -cos(need + x);
+//   every exact direction hits (theta_c + x0 < need: nothing to flag)  <=  ct > cosN + sinN x0.
+// delta: the rectangle's own (section 1).
+int sphere_rect(const View &v, const Rect &r, double &delta) {
+  const double ha = 0.5 * (r.a1 - r.a0), hb = 0.5 * (r.b1 - r.b0);
+  const V3 c = v.dir(r.a0 + ha, r.b0 + hb);
+  const double lc = norm(c), h = sqrt(ha * ha * v.uu + hb * hb * v.vv + 2.0 * ha * hb * v.uv), dmin = lc - h;
+  if (!(lc > 0.0) || !(h < 0.16 * lc)) return kUnbounded;  // h / dmin < 0.2
+  delta = 8.0 * ldexp(1.0, -24) * (v.m0 + r.a1 * v.mu + r.b1 * v.mv) / dmin + 4e-5;
+  const double ct = dot(c, v.axis) / lc, x0 = 1.01 * h / dmin, x = x0 + delta + 1e-9;
+  if (ct > v.cosN + v.sinN * x0) return kAllHit;
+  if (!(ct < v.cosN)) return kCentreHits;
+  const double L = v.cosN * (1.0 - 0.5 * x * x) - v.sinN * x;
+  return ct < L && ct > -L ? kClear : kUndecided;
+}
+// ... and, where one cone around the whole rectangle is too coarse (small frames: a packet spans
+// degrees), each of its quarters, down to 64 pieces; a piece whose centre ray hits settles it
+bool sphere_clear(const View &v, const Rect &r, int depth) {
+  double delta;
+  const int res = sphere_rect(v, r, delta);
+  if (res != kUndecided || depth == 3) return res == kClear;
+  const double am = 0.5 * (r.a0 + r.a1), bm = 0.5 * (r.b0 + r.b1);
+  return sphere_clear(v, {r.a0, am, r.b0, bm}, depth + 1) && sphere_clear(v, {am, r.a1, r.b0, bm}, depth + 1) &&
+         sphere_clear(v, {r.a0, am, bm, r.b1}, depth + 1) && sphere_clear(v, {am, r.a1, bm, r.b1}, depth + 1);
+}
+
+}  // namespace
+
+uint32_t void_packets(const VoidRequest &q, uint32_t *bits) {
+  memset(bits, 0, void_words(q.numTiles) * sizeof(uint32_t));
+  // only the raygen this certificate describes: woodcockTrackingWithAccel over the shell's spheres
+  if (q.raygen != IRT_RAYGEN_WITH_ACCEL || q.accelMode != IRT_ACCEL_SPHERE || q.mode != IRT_MODE_USER_GEOM) return 0;
+  if (q.W <= 0 || q.H <= 0 || q.tileStride <= 0 || q.tileBegin < 0) return 0;
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(q.cam[k])) return 0;
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(q.bmin[k]) || !std::isfinite(q.bmax[k])) return 0;
+  const double R = q.rOuter, r = q.rInner;
+  if (!std::isfinite(R) || !std::isfinite(r) || !(r >= 0.0) || !(R >= r) || !(R > 0.0)) return 0;
+  const V3 org = {q.cam[0], q.cam[1], q.cam[2]}, d00 = {q.cam[3], q.cam[4], q.cam[5]},
+           du = {q.cam[6], q.cam[7], q.cam[8]}, dv = {q.cam[9], q.cam[10], q.cam[11]};
+  const double eps = ldexp(1.0, -19);
+  const double P = norm(org);
+  if (!(P > 1.001 * R) || !(eps * P * P <= 0.01 * R * R)) return 0;  // eye inside, or too far away
+  const double need = asin(sqrt((R / P) * (R / P) + eps));            // theta must clear this
+  const V3 axis = (-1.0 / P) * org;
+  // T: the farthest box corner from the eye
+  double T = 0.0;
+  for (int k = 0; k < 8; ++k) {
+    const V3 cnr = {(k & 1) ? q.bmax[0] : q.bmin[0], (k & 2) ? q.bmax[1] : q.bmin[1], (k & 4) ? q.bmax[2] : q.bmin[2]};
+    T = std::max(T, norm(cnr + (-1.0) * org));
+  }
+  if (!(T < 1e9)) return 0;
+  const View v = {org, d00, du, dv, axis, dot(du, du), dot(dv, dv), fabs(dot(du, dv)), abs1(d00), abs1(du), abs1(dv),
+                  cos(need), sin(need)};
+  const int tilesX = (q.W + 63) / 64, total = tilesX * ((q.H + 63) / 64);
+  uint32_t count = 0;
+  auto in_box = [&](double a0, double a1, double b0, double b1, double delta) {
+    const double s = T * (delta + 4e-7);
+    double blo[3], bhi[3];
+    for (int j = 0; j < 3; ++j) {
+      blo[j] = (double)q.bmin[j] + s;
+      bhi[j] = (double)q.bmax[j] - s;
+      if (!(blo[j] < bhi[j])) return false;
+    }
+    return hits_box(org, v.dir(a0, b0), blo, bhi) && hits_box(org, v.dir(a1, b0), blo, bhi) &&
+           hits_box(org, v.dir(a0, b1), blo, bhi) && hits_box(org, v.dir(a1, b1), blo, bhi);
+  };
+  for (int k = 0; k < q.numTiles; ++k) {
+    const int tileId = q.tileList ? q.tileList[k] : q.tileBegin + k * q.tileStride;
+    if (tileId < 0 || tileId >= total) continue;
+    const int tx0 = (tileId % tilesX) * 64, ty0 = (tileId / tilesX) * 64;
+    // the tile as one rectangle first (its active pixels): most tiles lie wholly off the globe or
+    // wholly on it, and are settled by one test
+    double delta = 0.0;
+    const Rect tile = {tx0 + 0.5, std::min(tx0 + 64, q.W) + 0.5, ty0 + 0.5, std::min(ty0 + 64, q.H) + 0.5};
+    const int whole = sphere_rect(v, tile, delta);
+    if (whole == kAllHit) continue;
+    const bool tileVoid = whole == kClear && in_box(tile.a0, tile.a1, tile.b0, tile.b1, delta);
+    for (int j = 0; j < 64; ++j) {
+      const size_t p = (size_t)k * 64 + j;
+      const int sub = j >> 2, wave = j & 3;  // pixel_of (irt_raygen.h)
+      const int x0 = tx0 + (((sub & 3) << 4) | ((wave & 1) << 3)), y0 = ty0 + (((sub >> 2) << 4) | ((wave >> 1) << 3));
+      if (x0 >= q.W || y0 >= q.H) continue;  // no active pixel: nothing to merge
+      if (!tileVoid) {
+        // one past the last active pixel
+        const Rect r = {x0 + 0.5, std::min(x0 + 8, q.W) + 0.5, y0 + 0.5, std::min(y0 + 8, q.H) + 0.5};
+        double pd = 0.0;
+        if (sphere_rect(v, r, pd) < 0 || pd == 0.0) continue;  // (pd: the packet's own delta, for the box)
+        if (!sphere_clear(v, r, 0) || !in_box(r.a0, r.a1, r.b0, r.b1, pd)) continue;
+      }
+      bits[p >> 5] |= 1u << (p & 31);
+      ++count;
+    }
+  }
+  return count;
+}
+
+// The cache: one bitmap, kept while the request's key -- everything void_packets reads, the tile
+// list by content -- stays what it was (a progressive sequence computes it once).  With `defer`, a
+// new key is only noted, and the bitmap computed when the same request comes a second time: a
+// camera that gets one launch never pays for a bitmap no later launch would use.
+bool VoidCache::lookup(const VoidRequest &q, bool defer) {
+  std::vector<unsigned char> k(sizeof(VoidRequest) + (q.tileList ? (size_t)std::max(q.numTiles, 0) * sizeof(int32_t) : 0));
+  VoidRequest flat = q;
+  flat.tileList = q.tileList ? reinterpret_cast<const int32_t *>(1) : nullptr;  // a list by content, not by address
+  memcpy(k.data(), &flat, sizeof(flat));
+  if (q.tileList && q.numTiles > 0) memcpy(k.data() + sizeof(flat), q.tileList, (size_t)q.numTiles * sizeof(int32_t));
+  const bool same = keyed && k == key;
+  if (same && valid) return false;
+  if (!same) {
+    key.swap(k);
+    keyed = true;
+    valid = false;
+    count = 0;
+    if (defer) return false;
+  }
+  bits.assign(void_words(q.numTiles), 0u);
+  count = void_packets(q, bits.data());
+  valid = true;
+  ++generation;
+  return true;
+}
+
+}  // namespace irt

@@ -249,6 +249,8 @@ def default_kernel_id(ctx=None) -> int:
         L.irt_debug_slot_use.argtypes = [C.c_void_p, C.c_void_p]
         if v in ((d & ~4096), (d | 262144) & ~4096, (d | 1073741824) & ~4096) and L.irt_debug_slot_use(ctx._h, None) == 1:
             v |= 128  # kernel_for: the default kernels' OPT_SLOT form
+        elif ctx.void_use() > 0:
+            v |= 16  # ... their OPT_VOID form: the last launch carried a void-packet bitmap
         return v
     return int(L.irt_debug_default_variant()) & ~4096  # OPT_MONO: one kernel per frame
 
@@ -408,6 +410,51 @@ def deal_tiles(lp: LaunchParams, info: VolumeInfo, w: int, h: int, ranks: int,
     _check(lib().irt_deal_tiles(C.byref(lp), C.byref(info), w, h, ranks, rank0_extra,
                                 _ptr(table), table.size, C.byref(m)), "irt_deal_tiles")
     return table
+
+
+class VoidCache:
+    """irt_debug_void_packets with a cache of its own, as a context's launches keep one."""
+
+    def __init__(self):
+        L = lib()
+        L.irt_debug_void_cache_create.restype = C.c_void_p
+        L.irt_debug_void_cache_free.argtypes = [C.c_void_p]
+        L.irt_debug_void_cache_free.restype = None
+        self._h = C.c_void_p(L.irt_debug_void_cache_create())
+        self.computations = 0
+
+    def packets(self, lp, info, w, h, tile_begin=0, tile_stride=1, tiles=None):
+        out = void_packets(lp, info, w, h, tile_begin, tile_stride, tiles, cache=self)
+        return out
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().irt_debug_void_cache_free(self._h)
+            self._h = None
+
+
+def void_packets(lp: LaunchParams, info: VolumeInfo, w: int, h: int, tile_begin: int = 0,
+                 tile_stride: int = 1, tiles=None, cache: VoidCache = None) -> np.ndarray:
+    """irt_debug_void_packets: bool per packet of the launch (4 * block + wave, 64 per launch tile):
+    every ray of the packet, whatever the jitter, passes boxTest and misses the outer sphere."""
+    L = lib()
+    L.irt_debug_void_packets.argtypes = [C.c_void_p, C.POINTER(LaunchParams), C.POINTER(VolumeInfo), C.c_int,
+                                         C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_longlong)]
+    total = num_tiles(w, h)
+    t = None if tiles is None else np.ascontiguousarray(tiles, dtype=np.int32)
+    nt = len(t) if t is not None else (max(0, (total - tile_begin + tile_stride - 1) // tile_stride)
+                                       if tile_begin < total else 0)
+    bits = np.zeros(max(2 * nt, 1), np.uint32)
+    n, comp = C.c_uint32(), C.c_longlong()
+    _check(L.irt_debug_void_packets(cache._h if cache else None, C.byref(lp), C.byref(info), w, h, tile_begin,
+                                    tile_stride, _ptr(t) if t is not None else None, nt if t is not None else 0,
+                                    _ptr(bits), bits.size, C.byref(n), C.byref(comp)), "irt_debug_void_packets")
+    if cache:
+        cache.computations = comp.value
+    out = ((bits[:2 * nt, None] >> np.arange(32, dtype=np.uint32)[None, :]) & 1).astype(bool).reshape(-1)
+    assert int(out.sum()) == n.value
+    return out
 
 
 @dataclass
@@ -642,6 +689,16 @@ class Context:
         n, lg = C.c_int(), C.c_int()
         _check(L.irt_debug_sched_split(self._h, C.byref(n), C.byref(lg)), "irt_debug_sched_split")
         return n.value, lg.value
+
+    def void_use(self) -> int:
+        """Packets the last launch rendered as void (a chained launch of progressive frames renders
+        the packets that miss the globe in every frame once); 0: that path was not taken."""
+        L = lib()
+        if not hasattr(L, "irt_debug_void_use"):  # an older build loaded through IRT_LIB_PATH (A/B tools)
+            return 0
+        L.irt_debug_void_use.argtypes = [C.c_void_p]
+        L.irt_debug_void_use.restype = C.c_longlong
+        return L.irt_debug_void_use(self._h)
 
     def launch_workgroups(self, num_tiles: int, frames: int = 1) -> int:
         """Workgroups of one launch of num_tiles tiles x frames (the wg-trace buffer needs 4

@@ -188,6 +188,25 @@ int irt_debug_sched_split(const irt_context *ctx, int *numSplit, int *splitLg);
 int irt_debug_sched_order(const uint32_t *cost, int numBlocks, int tilesX, int tileStride, int policy,
                           int splitLg, float splitFactor, int numCU, int wavewg, size_t capacity,
                           uint32_t maxSplit, uint32_t *out, uint32_t *numSplit);
+/* Void packets (host/irt_void.cpp; no context, no device): the 8x8 packets of a launch of these
+ * parameters over a scene with these facts (bounds, sphericalBounds) all of whose rays, whatever the
+ * jitter, pass boxTest and miss the shell's outer sphere -- the packets a chained launch of several
+ * progressive frames renders once.  The launch's tiles as irt_render_tiles gives them (tileBegin,
+ * tileStride; a whole frame: 0, 1) or, with tileList, the listCount listed ones.  bits: one bit per
+ * packet, 4 * block + wave (16 blocks per launch tile), 2 words per tile, `capacity` words
+ * available; *numVoid: bits set.  With a cache (irt_debug_void_cache_create) the bitmap is computed
+ * only when the request differs from the cache's last one -- the context's launches keep one such
+ * cache --; *computations (may be NULL): bitmaps the cache has computed so far. */
+typedef struct irt_debug_void_cache irt_debug_void_cache;
+irt_debug_void_cache *irt_debug_void_cache_create(void);
+void irt_debug_void_cache_free(irt_debug_void_cache *cache);
+int irt_debug_void_packets(irt_debug_void_cache *cache, const irt_launch_params *lp, const irt_volume_info *info,
+                           int W, int H, int tileBegin, int tileStride, const int32_t *tileList, int listCount,
+                           uint32_t *bits, size_t capacity, uint32_t *numVoid, long long *computations);
+/* Packets the context's last launch rendered as void (0: the launch did not take that path -- a
+ * single frame, a sequence of views, unchained frames, the chain test hook set, a statistics or
+ * persistent variant, or no packet qualified); -1 for NULL. */
+long long irt_debug_void_use(const irt_context *ctx);
 /* Chained progressive frames on (default; IRT_CHAIN=0 turns it off per context) or off: a
  * launch of several frames (irt_render_accumulate, irt_render_tiles_accumulate,
  * irt_render_tile_list) lerps each frame straight into accum/fb, frame f's workgroup waiting for
