@@ -189,15 +189,18 @@ struct irt_context {
   float4 *d_frameCams = nullptr;
   float4 *h_frameCams = nullptr;
   size_t frameCamCap = 0;        // frames per slot
-  // void packets (RenderArgs::voidBits; host/irt_void.cpp): the bitmap of the last chained
-  // progressive launch's request (computed when the camera, frame, tiles or scene facts change), its
-  // device copy, and per launch slot the pinned staging an upload goes through (prepare_void)
+  // void packets (RenderArgs::voidList; host/irt_void.cpp): the bitmap and the work-item list of the
+  // last chained progressive launch's request (computed when the camera, frame, tiles or scene facts
+  // change), the list's device copy, and per launch slot the pinned staging an upload goes through
+  // (prepare_void)
   irt::VoidCache voidCache;
-  uint32_t *d_voidBits = nullptr;
-  uint32_t *h_voidBits = nullptr;
-  size_t voidCap = 0;            // words in d_voidBits, and per slot of h_voidBits
-  long long voidOnDevice = 0;    // the cache generation d_voidBits holds (0: none)
+  uint32_t *d_voidList = nullptr;
+  uint32_t *h_voidList = nullptr;
+  size_t voidCap = 0;            // words in d_voidList, and per slot of h_voidList
+  long long voidOnDevice = 0;    // the cache generation d_voidList holds (0: none)
+  bool voidOnDeviceList = false; // ... as the work-item list (else as the bitmap)
   long long lastVoid = 0;        // packets the last launch rendered as void (irt_debug_void_use)
+  long long lastWorkgroups = 0;  // the last launch's raygen grid (irt_debug_last_workgroups)
   // persistent launches (RenderArgs::queue, IRT_QUEUE=0|1): every resident wave pulls 8x8
   // packets from per-slot queue counters (kSlots x kQueueWords u32, zero between launches)
   bool queueOn = false;

@@ -41,7 +41,7 @@ void free_all(irt_context *c) {
   void *ptrs[] = {c->d_binHdr, c->d_fat, c->slot.slots, c->d_blocks, c->d_sphR, c->d_sphOff, c->d_sphRec,
                   c->d_sphBits, c->d_samples, c->d_maxOp, c->d_gridVR, c->d_gridMaxOp, c->d_gridBits, c->d_wOff, c->d_wRec, c->d_wBox, c->d_wTrig, c->d_schedOrder, c->d_schedCost, c->d_srgb, c->d_valueRanges,
                   c->d_lut, c->d_counters, c->d_counterBuckets, c->d_meta, c->d_queue, c->d_chainFlag,
-                  c->d_frameCams, c->d_tfStat, c->d_rects, c->d_updStat, c->d_probeCounts, c->d_voidBits};
+                  c->d_frameCams, c->d_tfStat, c->d_rects, c->d_updStat, c->d_probeCounts, c->d_voidList};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->d_cells) (void)hipFree(c->d_cells);
@@ -52,7 +52,7 @@ void free_all(irt_context *c) {
   if (c->h_schedOrder) (void)hipHostFree(c->h_schedOrder);
   if (c->h_frameCams) (void)hipHostFree(c->h_frameCams);
   if (c->h_chainFail) (void)hipHostFree(c->h_chainFail);
-  if (c->h_voidBits) (void)hipHostFree(c->h_voidBits);
+  if (c->h_voidList) (void)hipHostFree(c->h_voidList);
   for (LaunchSlot &r : c->ring) {
     if (r.ev0) (void)hipEventDestroy(r.ev0);
     if (r.ev1) (void)hipEventDestroy(r.ev1);

@@ -167,12 +167,36 @@ inline VoidRequest void_request(const irt_launch_params &lp, const irt_volume_in
   return q;
 }
 inline size_t void_words(int numTiles) { return ((size_t)(numTiles > 0 ? numTiles : 0) * 64 + 31) / 32; }
-// bits: void_words(numTiles) words; returns the number of packets flagged
-uint32_t void_packets(const VoidRequest &q, uint32_t *bits);
+// The work-item list of a launch that renders its void packets once (RenderArgs::voidList, k_render's
+// OPT_VOID forms), built in the classifier's pass; a packet is 4 * block + wave, as the bitmap numbers them.
+//   items[0 .. live)             the live part, the same for every frame (grid row) of the launch: the
+//                                packets with an active pixel that are not void.  Block b's packets sit
+//                                at indices = b mod 8, consecutive within that residue and blocks in
+//                                ascending order -- the hardware deals workgroup i to XCD i mod 8, so a
+//                                block's packets share one XCD's L2, as on the plain grid --; the
+//                                residues are padded to one length with empty items (~0u): live % 8 == 0.
+//   items[live .. live + count)  the void packets, ascending.  A launch of F frames deals them over its
+//                                rows, void_row(count, F) to a row: row y's item k is void packet
+//                                y * void_row + k, empty past the last.
+// Packets without an active pixel are in neither part: no workgroup is dispatched for them.
+// Empty (live == count == 0) when nothing is flagged: such a launch runs the plain grid.
+struct VoidLists {
+  std::vector<uint32_t> items;
+  uint32_t live = 0, count = 0;
+};
+constexpr uint32_t kVoidEmpty = ~0u;
+// void workgroups per grid row of a launch of F frames over `count` void packets: a multiple of 8, so
+// that with `live` every row starts on XCD 0
+inline uint32_t void_row(uint32_t count, int F) {
+  return (uint32_t)((((uint64_t)count + (uint64_t)F - 1) / (uint64_t)F + 7) & ~(uint64_t)7);
+}
+// bits: void_words(numTiles) words; returns the number of packets flagged.  lists (may be null): see above
+uint32_t void_packets(const VoidRequest &q, uint32_t *bits, VoidLists *lists = nullptr);
 // ... and the last request's bitmap, kept while the request stays the same (tile lists by content)
 struct VoidCache {
   std::vector<unsigned char> key;
   std::vector<uint32_t> bits;
+  VoidLists lists;                      // of the same request and generation as bits
   uint32_t count = 0;                   // packets flagged (0 while the bitmap is not computed)
   bool keyed = false, valid = false;    // a request was seen; its bitmap is computed
   long long generation = 0;             // bitmaps computed so far

@@ -138,12 +138,23 @@ struct RenderArgs {
   int slotBins;
   int slotSubs;
   // Void packets of a chained launch of progressive frames of one camera (host/irt_void.cpp; null:
-  // not in use): bit 4 block + wave set = every ray of that packet, whatever the jitter, passes
-  // boxTest and misses the outer sphere, so each frame only scales the pixel: nv = w_f 0 + (1 - w_f)
-  // old.  Frame 0's wave of such a packet applies all numSamples lerps in order and stores accum
-  // and fb once (irt_raygen.h void_packet); the later frames' waves return at once -- no hand-off, their
-  // publish words keep an earlier launch's epoch, which nothing waits for.
+  // not in use): every ray of such a packet, whatever the jitter, passes boxTest and misses the outer
+  // sphere, so each frame only scales the pixel: nv = w_f 0 + (1 - w_f) old.  One wave per launch
+  // applies all numSamples lerps in order and stores accum and fb once (irt_raygen.h void_packet);
+  // no other workgroup is dispatched for the packet -- no hand-off, its publish words keep an
+  // earlier launch's epoch, which nothing waits for.  Such a launch runs a grid of numSamples rows
+  // of voidLive + voidRow workgroups that read their packet (4 block + wave; ~0u: nothing) from
+  // voidList (irt_internal.h VoidLists): workgroup x < voidLive of row y renders frame y of packet
+  // voidList[x], as the plain grid's workgroup of that packet does; workgroup voidLive + k of row y
+  // renders void packet j = y voidRow + k, voidList[voidLive + j], if j < voidCount.
+  // (voidBits keeps its place: every other field's offset is the one the kernels without a void form
+  // were compiled with before the list came)
+  // The launches without a list (OPT_VLIST: the terrain kernels, and rows no shorter than the plain
+  // grid's) keep the plain grid and test the packet's bit, 4 block + wave: frame 0's wave of a void
+  // packet renders it, the later frames' waves return at once.
   const uint32_t *voidBits;
+  const uint32_t *voidList;
+  uint32_t voidLive, voidRow, voidCount;
 };
 // a persistent launch's queue words (irt_render.hip queue_take): 8 per-XCD counters and the
 // done count, each on its own 128-B line
@@ -207,8 +218,11 @@ enum : int {
                    // instead of the header, then the entry; launches on a scene with a table run
                    // this instantiation of the default kernels (kernel_for)
   OPT_VOID = 16,  // the default kernels' form for chained launches that carry a void-packet bitmap
-                  // (RenderArgs::voidBits; kernel_for): the packet's bit is tested at the kernel's top.
-                  // Every other launch runs the kernels without the test, as before
+                  // (RenderArgs::voidList; kernel_for): the workgroup's packet is read from the list at
+                  // the kernel's top.  Every other launch runs the kernels without it, as before
+  OPT_VLIST = 64,  // with OPT_VOID: the launch runs rows of work items (RenderArgs::voidList) instead
+                   // of the plain grid with the bitmap; the flat kernel only (the terrain kernels'
+                   // list form needs scratch), and only where the rows are shorter than the plain grid's
   // bits 8-11: minimum waves per SIMD asked of the register allocator (0: none)
 };
 // OPT_MONO is kept in the numbering of round 1 (the one-kernel raygen; the setup -> march ->
@@ -265,8 +279,10 @@ bool render_queue_compiled();  // the A/B library (make VARIANTS=all) only
 // the default kernels with one-wave workgroups
 bool render_split_ok(const RenderArgs &A, int variant);
 // whether a chained launch of `variant` with these arguments can merge its void packets
-// (RenderArgs::voidBits): the default kernels with one-wave workgroups, without the slot table
+// (RenderArgs::voidList): the default kernels with one-wave workgroups, without the slot table
 bool render_void_ok(const RenderArgs &A, int variant);
+// ... and whether it then runs the work-item list (else the bitmap on the plain grid)
+bool render_void_list_ok(int variant);
 // workgroups a persistent launch of `variant` runs on a device with numCU compute units:
 // every slot the kernel's occupancy allows (resident at once), at most `numBlocks`
 int render_queue_wgs(const RenderArgs &A, int variant, int numCU, int numBlocks);

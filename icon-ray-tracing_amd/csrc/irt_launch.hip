@@ -580,45 +580,68 @@ int setup_chain(irt_context *c, int numFrames, Launch &L) {
   return IRT_OK;
 }
 
-// Void packets (RenderArgs::voidBits, host/irt_void.cpp): chained progressive frames of one camera
-// render the packets that can only ever give the zero colour once per launch.  Only launches that
-// can use the bitmap compute it -- several chained frames of one camera through the default
-// kernels (render_void_ok), the raygen over the shell's spheres; not with the chain test hook set
+// Void packets (RenderArgs::voidList, host/irt_void.cpp): chained progressive frames of one camera
+// render the packets that can only ever give the zero colour once per launch, and dispatch no other
+// workgroup for them: the launch runs rows of work items (VoidLists) instead of the plain grid, so
+// its workgroup count (L.numWG: the count ring, irt_debug_last_workgroups) is set here, before the
+// counters are chosen.  Only launches that can use the list compute it -- several chained frames of
+// one camera through the default kernels (render_void_ok), the raygen over the shell's spheres, at
+// most 65,535 of them (a grid's rows: a void wave's counts, 64 x numFrames, then fit its 32-bit
+// words); not with the chain test hook set
 // (its withheld frame must stall every packet), a measurement-only exit or the statistics and
 // timing variants (their per-wave figures) -- and the cache computes it only when the same request
 // comes a second time (VoidCache::lookup, defer): a progressive sequence once, at its second
 // launch (0.4 ms of host time at 1024^2, 0.8 ms at 2048^2 -- DESIGN.md section 5.1 -- against 0.02
 // and 0.1 ms saved per launch of 8 frames); a camera that gets one launch, and a new camera with
-// single-frame launches, never.  The device copy is one buffer, as d_frameCams and d_chainFlag are:
-// it is rewritten on the launching stream when the cache has computed a new bitmap, which is behind
+// single-frame launches, never.  The list does not depend on the number of frames (the rows' void
+// parts are dealt from it by index).  The device copy is one buffer, as d_frameCams and d_chainFlag
+// are: it is rewritten on the launching stream when the cache has computed a new list (or the launch
+// needs the other of list and bitmap), which is behind
 // every launch that reads the old one only because a context's launches run in call order, also
 // across streams (claim_slot); the upload goes through this launch slot's pinned staging.
 int prepare_void(irt_context *c, const irt_launch_params *lp, const RenderRequest &r, Launch &L) {
   RenderArgs &A = L.A;
   c->lastVoid = 0;
-  if (!(A.chain && !r.seq && r.numFrames > 1 && L.numTiles > 0 && c->chainWithhold < 0 && c->probeExit == 0 &&
-        !stats_variant(c) && lp->raygen == IRT_RAYGEN_WITH_ACCEL && lp->accelMode == IRT_ACCEL_SPHERE &&
+  if (!(A.chain && !r.seq && r.numFrames > 1 && r.numFrames <= 65535 && L.numTiles > 0 &&
+        c->chainWithhold < 0 && c->probeExit == 0 && !stats_variant(c) &&
+        lp->raygen == IRT_RAYGEN_WITH_ACCEL && lp->accelMode == IRT_ACCEL_SPHERE &&
         render_void_ok(A, c->variant)))
     return IRT_OK;
   c->voidCache.lookup(void_request(*lp, c->info, r.W, r.H, r.tileBegin, r.tileStride, L.numTiles, r.tileList), true);
-  if (!c->voidCache.count) return IRT_OK;
-  const size_t words = void_words(L.numTiles);
+  const VoidLists &vl = c->voidCache.lists;
+  if (!c->voidCache.count || vl.items.empty()) return IRT_OK;
+  // The flat kernel: the work-item list, where its rows are shorter than the plain grid's (in a tiny
+  // frame the residues' padding can outweigh the merged packets: 64x64 FRAMING, 64 + 8 against 64) --
+  // so no launch has more workgroups than irt_debug_launch_workgroups says.  Every other launch: the
+  // bitmap on the plain grid (the terrain kernels always).
+  const bool list = render_void_list_ok(c->variant) &&
+                    (size_t)vl.live + void_row(vl.count, r.numFrames) < (size_t)L.numTiles * 64;
+  const size_t words = list ? vl.items.size() : void_words(L.numTiles);
   if (words > c->voidCap) {
     // every launch that may still read the old words, on any stream, and every slot's staging
     int rc = grow(c, Retire::SlotsThenStream, L.s, &c->voidCap, words,
-                  {{(void **)&c->d_voidBits, [](size_t n) { return n * sizeof(uint32_t); }, false},
-                   {(void **)&c->h_voidBits, [](size_t n) { return kSlots * n * sizeof(uint32_t); }, true}},
+                  {{(void **)&c->d_voidList, [](size_t n) { return n * sizeof(uint32_t); }, false},
+                   {(void **)&c->h_voidList, [](size_t n) { return kSlots * n * sizeof(uint32_t); }, true}},
                   nullptr);
     c->voidOnDevice = 0;
     if (rc) return rc;
   }
-  if (c->voidOnDevice != c->voidCache.generation) {
-    uint32_t *h = c->h_voidBits + (size_t)L.slot * c->voidCap;
-    memcpy(h, c->voidCache.bits.data(), words * sizeof(uint32_t));
-    IRT_HIP(hipMemcpyAsync(c->d_voidBits, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, L.s));
+  if (c->voidOnDevice != c->voidCache.generation || c->voidOnDeviceList != list) {
+    uint32_t *h = c->h_voidList + (size_t)L.slot * c->voidCap;
+    memcpy(h, list ? vl.items.data() : c->voidCache.bits.data(), words * sizeof(uint32_t));
+    c->voidOnDeviceList = list;
+    IRT_HIP(hipMemcpyAsync(c->d_voidList, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, L.s));
     c->voidOnDevice = c->voidCache.generation;
   }
-  A.voidBits = c->d_voidBits;
+  if (list) {
+    A.voidList = c->d_voidList;
+    A.voidLive = vl.live;
+    A.voidRow = void_row(vl.count, r.numFrames);
+    A.voidCount = vl.count;
+    L.numWG = ((size_t)A.voidLive + A.voidRow) * (size_t)r.numFrames;  // launch_variant's grid
+  } else {
+    A.voidBits = c->d_voidList;
+  }
   c->lastVoid = c->voidCache.count;
   return IRT_OK;
 }
@@ -674,6 +697,7 @@ int launch_and_commit(irt_context *c, Launch &L) {
   LaunchSlot &r = c->ring[L.slot];
   c->schedLastApplied = A.schedOrder != nullptr;
   c->lastNumSplit = A.numSplit;
+  c->lastWorkgroups = L.numTiles > 0 ? (long long)L.numWG : 0;
   c->schedApplied += c->schedLastApplied ? 1 : 0;
   // the 16-counter block (device atomics) is only needed by the statistics variant and the
   // IRT_COUNTERS=atomic mode; it must start zeroed
@@ -729,7 +753,7 @@ int render_impl(irt_context *c, const irt_launch_params *lp, const RenderRequest
   decide_queue(c, r.numFrames, L);
   if ((rc = decide_sched(c, lp, r, L))) return rc;
   count_workgroups(c, r, L);
-  if ((rc = choose_counters(c, L)) || (rc = setup_chain(c, r.numFrames, L)) || (rc = prepare_void(c, lp, r, L)) ||
+  if ((rc = prepare_void(c, lp, r, L)) || (rc = choose_counters(c, L)) || (rc = setup_chain(c, r.numFrames, L)) ||
       (rc = stage_sequence(c, r, L)) ||
       (rc = ensure_samples(c, r.numFrames, L)))
     return rc;

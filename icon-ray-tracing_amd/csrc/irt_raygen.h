@@ -261,15 +261,21 @@ __device__ __forceinline__ void flush_counters(const RenderArgs &A, const uint32
   }
 }
 
-// A void packet of a chained launch (RenderArgs::voidBits): in every frame each of its rays passes
+// A void packet of a chained launch (RenderArgs::voidList): in every frame each of its rays passes
 // boxTest and misses both spheres -- numRanges == 0, colour (0, 0, 0, 0) -- so frame g only lerps
-// the zero colour into the pixel.  Frame 0's wave does that for every frame of the launch, in frame
-// order and with write_pixel_chain's expressions (the products and sums stay: w * 0 + -0 is +0, and
-// NaN or inf in accum go through as they would), then stores accum and the RGBA8 of the final value
-// once, with the streaming stores the launch's last frame uses; the later frames' waves do nothing.
-// The wave's counts are those of its frames' waves (rays launched = rays in the box = active
-// pixels), stored or added as flush_counters does; no LDS, no wait, no publish.
-__device__ __forceinline__ void void_packet(const RenderArgs &KA, uint32_t blk, int pwave, int frame) {
+// the zero colour into the pixel.  The packet's one wave of the launch -- in whichever grid row its
+// item sits: the packet depends on nothing inside the launch, and nothing in it on the packet --
+// does that for every frame, in frame order and with write_pixel_chain's expressions (the products
+// and sums stay: w * 0 + -0 is +0, and NaN or inf in accum go through as they would), then stores
+// accum and the RGBA8 of the final value once, with the streaming stores the launch's last frame uses.
+// The wave's counts are those of the numSamples waves the plain grid runs for the packet (rays
+// launched = rays in the box = active pixels, once per frame: at most 64 x 65,535 rows, within the
+// per-workgroup 32-bit word), stored or added as flush_counters does; no LDS, no wait, no publish.
+// An empty item (~0u, the lists' padding) stores its zero counts and returns.  The bitmap form on the
+// plain grid (RenderArgs::voidBits): frame 0's wave renders, every frame's wave reports its own counts.
+// lerp: this wave renders the packet (the bitmap form: frame 0's wave; a list item: unless empty);
+// frames: the frames whose counts the wave reports (the bitmap form: its own, 1; a list item: all).
+__device__ __forceinline__ void void_packet(const RenderArgs &KA, uint32_t blk, int pwave, bool lerp, uint32_t frames) {
   // the launch's arguments through a per-lane pointer, as chain_replay_fb reads them: vector loads
   // into VGPRs, all free here, and none of the raygen's scarce SGPRs
   const RenderArgs *vp = &KA;
@@ -277,7 +283,7 @@ __device__ __forceinline__ void void_packet(const RenderArgs &KA, uint32_t blk, 
   const RenderArgs &A = *vp;
   const int lane = (int)__lane_id();
   const Pixel px = pixel_of(A, blk, pwave * 64 + lane);
-  if (frame == 0 && px.active) {
+  if (lerp && px.active) {
     float4 nv = A.accum[px.outIdx];
     const float c = 0.f;
 #pragma nounroll
@@ -297,7 +303,7 @@ __device__ __forceinline__ void void_packet(const RenderArgs &KA, uint32_t blk, 
     __builtin_nontemporal_store(rgba, &A.fb[px.outIdx]);
   }
   if (A.counters) {
-    const uint32_t n = (uint32_t)__popcll(__ballot(px.active));
+    const uint32_t n = (uint32_t)__popcll(__ballot(px.active)) * frames;
     const size_t wg = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
     if (A.wgCounts) {
       if (lane < kCnt) A.wgCounts[wg * kCnt + lane] = lane < 2 ? n : 0u;

@@ -99,15 +99,29 @@ __global__ void __launch_bounds__((OPT & OPT_WAVEWG) ? 64 : 256,
     w[3] = __builtin_amdgcn_s_getreg((15 << 11) | 20);  // HW_REG_XCC_ID
   }
   if (A.probeExit == 1) return;  // measurement only
-  // Void packets (OPT_VOID: the kernels of launches with A.voidBits -- chained progressive frames of
-  // one camera; irt_launch.hip prepare_void, kernel_for): the packet's bit, by the scalar unit,
-  // before anything else is in flight -- the prologue's LDS-DMA included.  Such a launch has no
-  // block order and no split items, so the workgroup's packet is the one the grid deal below gives it.
+  // Void packets (OPT_VOID: the kernels of launches with A.voidList -- chained progressive frames of
+  // one camera; irt_launch.hip prepare_void, kernel_for): the workgroup's packet from the launch's
+  // work-item list, by the scalar unit, before anything else is in flight -- the prologue's LDS-DMA
+  // included.  Such a launch has no block order and no split items.  Row (blockIdx.y = frame) y is
+  // voidLive live items, the same in every row, then voidRow void items (RenderArgs::voidList).
+  //   No deadlock: a live packet's wave of frame y waits for its wave of frame y - 1 alone, which has
+  // the same blockIdx.x one row up and so is dispatched before it (rows are dispatched in order);
+  // void and empty items wait for nothing.
+  //   XCD locality: voidLive + voidRow is a multiple of 8, so every row starts on XCD 0 and workgroup x
+  // runs on XCD x % 8; block b's live packets sit at x = b mod 8 (VoidLists), so they share that XCD's
+  // L2 in every frame, as on the plain grid.
+  //   The terrain kernels' list form leaves the resource gate (8 B of scratch, profiles/r09a_compact/
+  // resources.txt), so only the flat kernel has one (OPT_VLIST); the others keep the bitmap on the
+  // plain grid: the packet's bit (RenderArgs::voidBits), frame 0's wave renders the void packet and
+  // the later frames' waves return at once.
   constexpr bool kVoid = (OPT & OPT_VOID) != 0;
+  constexpr bool kList = kVoid && (OPT & OPT_VLIST) != 0;
+  static_assert(kVoid || (OPT & OPT_VLIST) == 0, "OPT_VLIST: a form of the OPT_VOID kernels");
+  uint32_t vitem = 0u;  // kList: this workgroup's packet (4 block + wave)
   static_assert(!kVoid || (wavewg && lean && Tracer<OPT>::kCoop &&
                            (OPT & (OPT_SPLIT | OPT_SLOT | OPT_STATS | OPT_TIMING | OPT_QUEUE | OPT_GRID | OPT_WEDGE)) == 0),
                 "void packets: the default kernels' plain grid form");
-  if constexpr (kVoid) {
+  if constexpr (kVoid && !kList) {
     // (the arguments through fresh_args(): nothing this test loads stays live into the raygen)
     const RenderArgs &VA = fresh_args();
     const uint32_t vb = blockIdx.x, vwave = (vb >> 3) & 3u;
@@ -115,7 +129,25 @@ __global__ void __launch_bounds__((OPT & OPT_WAVEWG) ? 64 : 256,
     uint32_t isVoid = VA.voidBits ? (scalar_word(VA.voidBits, vpkt >> 5) >> (vpkt & 31u)) & 1u : 0u;
     asm volatile("" : "+s"(isVoid));  // one opaque scalar branch: the raygen below compiles as without it
     if (isVoid) {
-      void_packet(VA, vblk, (int)vwave, (int)blockIdx.y);
+      void_packet(VA, vblk, (int)vwave, blockIdx.y == 0, 1u);
+      return;
+    }
+  }
+  if constexpr (kList) {
+    const RenderArgs &VA = fresh_args();
+    const uint32_t vx = blockIdx.x, vlive = VA.voidLive;
+    // row y's void item k: void packet j = y voidRow + k, if there is one
+    const uint32_t j = blockIdx.y * VA.voidRow + (vx - vlive);
+    const bool inVoid = vx >= vlive, none = inVoid && j >= VA.voidCount;
+    // (always a read inside the list's voidLive + voidCount words, voidCount > 0)
+    const uint32_t w = scalar_word(VA.voidList, none ? 0u : inVoid ? vlive + j : vx);
+    vitem = __builtin_amdgcn_readfirstlane(none ? ~0u : w);
+    // void items and the padding (~0u, in either part) end here, before the prologue
+    uint32_t leave = __builtin_amdgcn_readfirstlane(inVoid || vitem == ~0u ? 1u : 0u);
+    asm volatile("" : "+s"(leave));  // one opaque scalar branch: the raygen below compiles as without it
+    if (leave) {
+      const bool some = vitem != ~0u;
+      void_packet(VA, some ? vitem >> 2 : 0u, (int)(some ? vitem & 3u : 0u), some, some ? (uint32_t)VA.numSamples : 0u);
       return;
     }
   }
@@ -205,7 +237,7 @@ __global__ void __launch_bounds__((OPT & OPT_WAVEWG) ? 64 : 256,
     }
   }
   const uint32_t wg = split ? (((bx >> 3) / kNwb) << 3) | (bx & 7u) : bx;
-  const int wwave = partSel >= 0 ? (int)(splitP & 3u)
+  const int wwave = kList ? (int)(vitem & 3u) : partSel >= 0 ? (int)(splitP & 3u)
                                   : split ? (int)(((bx >> 3) % kNwb) * kWpg) : 0;  // the block's first wave in this workgroup
   const int ptid = split ? wwave * 64 + tid : tid;
   if constexpr ((OPT & OPT_TIMING) != 0) {
@@ -216,7 +248,7 @@ __global__ void __launch_bounds__((OPT & OPT_WAVEWG) ? 64 : 256,
   // grid.y = frame k of a progressive batch (accumID + k), whose colour goes to the sample
   // buffer for k_accumulate; a single frame writes accum/fb directly.  With measured-cost
   // scheduling (irt_context.hip) workgroup b renders block order[b].
-  const uint32_t blk = partSel >= 0 ? splitP >> 2 : A.schedOrder ? scalar_word(A.schedOrder, wg) : wg;  // uniform: an SGPR
+  const uint32_t blk = kList ? vitem >> 2 : partSel >= 0 ? splitP >> 2 : A.schedOrder ? scalar_word(A.schedOrder, wg) : wg;  // uniform: an SGPR
   // a split packet's regular workgroup: nothing to render (its counts and trace are still written)
   const uint32_t pkt = blk * 4u + (uint32_t)wwave;
   const bool splitAway = splitOk && partSel < 0 && ((scalar_word(A.splitMask, pkt >> 5) >> (pkt & 31u)) & 1u);
@@ -560,6 +592,7 @@ bool render_split_ok(const RenderArgs &A, int variant) {
 }
 
 // (kernel_for then picks the OPT_VOID form, which has no OPT_SLOT or OPT_SPLIT sibling)
+bool render_void_list_ok(int variant) { return variant == (kDefaultVariant | kNoMissBit); }
 bool render_void_ok(const RenderArgs &A, int variant) {
   return render_split_ok(A, variant) && !A.slots && !A.queue && !A.numSplit && !A.schedOrder;
 }
@@ -605,8 +638,11 @@ RenderKernel kernel_for(const RenderArgs &A, int &threads) {
   // and a scene with a slot table: their OPT_SLOT form
   if constexpr (K == (kDefaultVariant & ~OPT_MONO) || K == ((kDefaultVariant | kNoMissBit) & ~OPT_MONO) ||
                 K == ((kDefaultVariant | OPT_VOIDLOC) & ~OPT_MONO)) {
-    // chained progressive frames with a void-packet bitmap (render_void_ok: no table, no split items)
-    if (A.voidBits) return k_render<K | OPT_VOID>;
+    // chained progressive frames with a void-packet work-item list (render_void_ok: no table, no
+    // split items)
+    if constexpr (K == ((kDefaultVariant | kNoMissBit) & ~OPT_MONO))
+      if (A.voidList) return k_render<K | OPT_VOID | OPT_VLIST>;
+    if (A.voidBits) return k_render<K | OPT_VOID>;  // (the terrain kernels: the bitmap, the plain grid)
     if (A.slots) return A.numSplit ? k_render<K | OPT_SPLIT | OPT_SLOT> : k_render<K | OPT_SLOT>;
     if (A.numSplit) return k_render<K | OPT_SPLIT>;
   }
@@ -622,7 +658,9 @@ void launch_variant(const RenderArgs &A, int numBlocks, hipStream_t s) {
     numBlocks = A.numTiles * 16;
   } else {
     const int split = A.numSplit ? (int)A.numSplit : 0;  // the listed work items first (kernel_for: OPT_SPLIT)
-    hipLaunchKernelGGL(k, dim3(numBlocks * (256 / threads) + split, A.numSamples), dim3(threads), 0, s, A);
+    // a launch with a void-packet list (kernel_for: OPT_VOID): its rows of live and void items
+    const uint32_t gx = A.voidList ? A.voidLive + A.voidRow : (uint32_t)(numBlocks * (256 / threads) + split);
+    hipLaunchKernelGGL(k, dim3(gx, A.numSamples), dim3(threads), 0, s, A);
   }
   // progressive batch: the lerp chain over the frames' samples (chained frames lerp in k_render)
   if (A.numSamples > 1 && !A.chain) hipLaunchKernelGGL(k_accumulate, dim3(numBlocks), dim3(256), 0, s, A);
@@ -674,9 +712,13 @@ void prewarm_variant(hipStream_t s) {
   const RenderKernel kt = kernel_for<N>(A, threads);
   if (kt != k) hipLaunchKernelGGL(kt, dim3(1), dim3(threads), 0, s, A);
   A.slots = nullptr;
-  A.voidBits = reinterpret_cast<const uint32_t *>(16);  // the void-packet form (never dereferenced)
+  A.voidList = reinterpret_cast<const uint32_t *>(16);  // the void-packet form (never dereferenced)
   const RenderKernel kv = kernel_for<N>(A, threads);
   if (kv != k) hipLaunchKernelGGL(kv, dim3(1), dim3(threads), 0, s, A);
+  A.voidList = nullptr;
+  A.voidBits = reinterpret_cast<const uint32_t *>(16);  // and the bitmap form (likewise)
+  const RenderKernel kb = kernel_for<N>(A, threads);
+  if (kb != k && kb != kv) hipLaunchKernelGGL(kb, dim3(1), dim3(threads), 0, s, A);
   A.voidBits = nullptr;
   A.queue = reinterpret_cast<uint32_t *>(16);  // never dereferenced: the kernel returns first
   const RenderKernel kq = kernel_for<N>(A, threads);

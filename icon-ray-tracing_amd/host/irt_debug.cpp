@@ -241,4 +241,41 @@ int irt_debug_void_packets(irt_debug_void_cache *cache, const irt_launch_params 
   return IRT_OK;
 }
 
+int irt_debug_void_lists(irt_debug_void_cache *cache, const irt_launch_params *lp, const irt_volume_info *info,
+                         int W, int H, int tileBegin, int tileStride, const int32_t *tileList, int listCount,
+                         int numFrames, uint32_t *items, size_t capacity, uint32_t *numLive, uint32_t *voidPerRow,
+                         uint32_t *numVoid) {
+  if (!lp || !info || !numLive || !voidPerRow || !numVoid || W <= 0 || H <= 0 || tileBegin < 0 || tileStride <= 0 ||
+      listCount < 0 || numFrames < 1) {
+    set_error("irt_debug_void_lists: bad argument");
+    return IRT_E_INVALID;
+  }
+  const int total = ((W + 63) / 64) * ((H + 63) / 64);
+  const int numTiles = tileList ? listCount : tileBegin < total ? (total - tileBegin + tileStride - 1) / tileStride : 0;
+  for (int k = 0; tileList && k < listCount; ++k)
+    if (tileList[k] < 0 || tileList[k] >= total) {
+      set_error("irt_debug_void_lists: tile id %d at %d outside [0, %d)", tileList[k], k, total);
+      return IRT_E_INVALID;
+    }
+  const VoidRequest q = void_request(*lp, *info, W, H, tileBegin, tileStride, numTiles, tileList);
+  VoidCache local;
+  VoidCache &vc = cache ? cache->c : local;
+  vc.lookup(q);
+  const VoidLists &vl = vc.lists;
+  *numLive = vl.live;
+  *numVoid = vl.count;
+  *voidPerRow = vl.count ? void_row(vl.count, numFrames) : 0u;
+  if (!items) return IRT_OK;
+  const size_t need = (size_t)vl.live + (size_t)numFrames * *voidPerRow;
+  if (need > capacity) {
+    set_error("irt_debug_void_lists: %zu words needed", need);
+    return IRT_E_INVALID;
+  }
+  // the rows' void parts as k_render's workgroups read them: item y * voidPerRow + k, empty past the last
+  std::copy(vl.items.begin(), vl.items.begin() + vl.live, items);
+  for (size_t j = 0; j < (size_t)numFrames * *voidPerRow; ++j)
+    items[vl.live + j] = j < vl.count ? vl.items[vl.live + j] : kVoidEmpty;
+  return IRT_OK;
+}
+
 }  // extern "C"

@@ -60,6 +60,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "irt_internal.h"
 
@@ -138,8 +139,9 @@ bool sphere_clear(const View &v, const Rect &r, int depth) {
 
 }  // namespace
 
-uint32_t void_packets(const VoidRequest &q, uint32_t *bits) {
+uint32_t void_packets(const VoidRequest &q, uint32_t *bits, VoidLists *lists) {
   memset(bits, 0, void_words(q.numTiles) * sizeof(uint32_t));
+  if (lists) *lists = VoidLists();
   // only the raygen this certificate describes: woodcockTrackingWithAccel over the shell's spheres
   if (q.raygen != IRT_RAYGEN_WITH_ACCEL || q.accelMode != IRT_ACCEL_SPHERE || q.mode != IRT_MODE_USER_GEOM) return 0;
   if (q.W <= 0 || q.H <= 0 || q.tileStride <= 0 || q.tileBegin < 0) return 0;
@@ -167,6 +169,9 @@ uint32_t void_packets(const VoidRequest &q, uint32_t *bits) {
                   cos(need), sin(need)};
   const int tilesX = (q.W + 63) / 64, total = tilesX * ((q.H + 63) / 64);
   uint32_t count = 0;
+  // the work items, gathered in this pass: the live packets per residue of their block (mod 8), in
+  // block then wave order, and the void ones
+  std::vector<uint32_t> res[8], voids;
   auto in_box = [&](double a0, double a1, double b0, double b1, double delta) {
     const double s = T * (delta + 4e-7);
     double blo[3], bhi[3];
@@ -180,30 +185,46 @@ uint32_t void_packets(const VoidRequest &q, uint32_t *bits) {
   };
   for (int k = 0; k < q.numTiles; ++k) {
     const int tileId = q.tileList ? q.tileList[k] : q.tileBegin + k * q.tileStride;
-    if (tileId < 0 || tileId >= total) continue;
+    if (tileId < 0 || tileId >= total) continue;  // (no launch has such a tile)
     const int tx0 = (tileId % tilesX) * 64, ty0 = (tileId / tilesX) * 64;
     // the tile as one rectangle first (its active pixels): most tiles lie wholly off the globe or
     // wholly on it, and are settled by one test
     double delta = 0.0;
     const Rect tile = {tx0 + 0.5, std::min(tx0 + 64, q.W) + 0.5, ty0 + 0.5, std::min(ty0 + 64, q.H) + 0.5};
     const int whole = sphere_rect(v, tile, delta);
-    if (whole == kAllHit) continue;
+    if (whole == kAllHit && !lists) continue;
     const bool tileVoid = whole == kClear && in_box(tile.a0, tile.a1, tile.b0, tile.b1, delta);
     for (int j = 0; j < 64; ++j) {
       const size_t p = (size_t)k * 64 + j;
       const int sub = j >> 2, wave = j & 3;  // pixel_of (irt_raygen.h)
       const int x0 = tx0 + (((sub & 3) << 4) | ((wave & 1) << 3)), y0 = ty0 + (((sub >> 2) << 4) | ((wave >> 1) << 3));
-      if (x0 >= q.W || y0 >= q.H) continue;  // no active pixel: nothing to merge
-      if (!tileVoid) {
+      if (x0 >= q.W || y0 >= q.H) continue;  // no active pixel: nothing to merge, and no work item
+      bool isVoid = tileVoid;
+      if (!tileVoid && whole != kAllHit) {
         // one past the last active pixel
         const Rect r = {x0 + 0.5, std::min(x0 + 8, q.W) + 0.5, y0 + 0.5, std::min(y0 + 8, q.H) + 0.5};
-        double pd = 0.0;
-        if (sphere_rect(v, r, pd) < 0 || pd == 0.0) continue;  // (pd: the packet's own delta, for the box)
-        if (!sphere_clear(v, r, 0) || !in_box(r.a0, r.a1, r.b0, r.b1, pd)) continue;
+        double pd = 0.0;  // (pd: the packet's own delta, for the box)
+        isVoid = !(sphere_rect(v, r, pd) < 0 || pd == 0.0) && sphere_clear(v, r, 0) && in_box(r.a0, r.a1, r.b0, r.b1, pd);
+      }
+      if (!isVoid) {
+        if (lists) res[(p >> 2) & 7].push_back((uint32_t)p);
+        continue;
       }
       bits[p >> 5] |= 1u << (p & 31);
+      if (lists) voids.push_back((uint32_t)p);
       ++count;
     }
+  }
+  if (lists && count) {
+    // residue x's k-th packet at index 8 k + x; every residue padded to the longest
+    size_t len = 0;
+    for (const auto &r : res) len = std::max(len, r.size());
+    lists->live = (uint32_t)(8 * len);
+    lists->count = count;
+    lists->items.assign(8 * len + voids.size(), kVoidEmpty);
+    for (size_t x = 0; x < 8; ++x)
+      for (size_t k = 0; k < res[x].size(); ++k) lists->items[8 * k + x] = res[x][k];
+    std::copy(voids.begin(), voids.end(), lists->items.begin() + 8 * len);
   }
   return count;
 }
@@ -228,7 +249,7 @@ bool VoidCache::lookup(const VoidRequest &q, bool defer) {
     if (defer) return false;
   }
   bits.assign(void_words(q.numTiles), 0u);
-  count = void_packets(q, bits.data());
+  count = void_packets(q, bits.data(), &lists);
   valid = true;
   ++generation;
   return true;

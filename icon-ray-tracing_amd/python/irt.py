@@ -457,6 +457,34 @@ def void_packets(lp: LaunchParams, info: VolumeInfo, w: int, h: int, tile_begin:
     return out
 
 
+def void_lists(lp: LaunchParams, info: VolumeInfo, w: int, h: int, frames: int, tile_begin: int = 0,
+               tile_stride: int = 1, tiles=None, cache: VoidCache = None):
+    """irt_debug_void_lists: the work items of a chained launch of `frames` frames that renders its void
+    packets once -- (live, void): live (Lp,) uint32, the live part every grid row shares; void (frames, Vr)
+    uint32, each row's void part; packets as 4 * block + wave, 0xFFFFFFFF an empty item.  None when
+    the request has no void packet (the launch runs the plain grid)."""
+    L = lib()
+    L.irt_debug_void_lists.argtypes = [C.c_void_p, C.POINTER(LaunchParams), C.POINTER(VolumeInfo), C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    t = None if tiles is None else np.ascontiguousarray(tiles, dtype=np.int32)
+    live, row, n = C.c_uint32(), C.c_uint32(), C.c_uint32()
+
+    def call(items):
+        _check(L.irt_debug_void_lists(cache._h if cache else None, C.byref(lp), C.byref(info), w, h, tile_begin,
+                                      tile_stride, _ptr(t) if t is not None else None, len(t) if t is not None else 0,
+                                      frames, _ptr(items) if items is not None else None,
+                                      items.size if items is not None else 0, C.byref(live), C.byref(row), C.byref(n)),
+               "irt_debug_void_lists")
+
+    call(None)
+    if n.value == 0:
+        return None
+    items = np.zeros(live.value + frames * row.value, np.uint32)
+    call(items)
+    return items[:live.value].copy(), items[live.value:].reshape(frames, row.value).copy()
+
+
 @dataclass
 class FrameSetup:
     """What icon_rt's main() derives before the first launch (hostCode.cu:736-958)."""
@@ -699,6 +727,13 @@ class Context:
         L.irt_debug_void_use.argtypes = [C.c_void_p]
         L.irt_debug_void_use.restype = C.c_longlong
         return L.irt_debug_void_use(self._h)
+
+    def last_workgroups(self) -> int:
+        """Workgroups the last launch dispatched for its raygen (grid x * grid y)."""
+        L = lib()
+        L.irt_debug_last_workgroups.argtypes = [C.c_void_p]
+        L.irt_debug_last_workgroups.restype = C.c_longlong
+        return L.irt_debug_last_workgroups(self._h)
 
     def launch_workgroups(self, num_tiles: int, frames: int = 1) -> int:
         """Workgroups of one launch of num_tiles tiles x frames (the wg-trace buffer needs 4

@@ -207,6 +207,25 @@ int irt_debug_void_packets(irt_debug_void_cache *cache, const irt_launch_params 
  * single frame, a sequence of views, unchained frames, the chain test hook set, a statistics or
  * persistent variant, or no packet qualified); -1 for NULL. */
 long long irt_debug_void_use(const irt_context *ctx);
+/* The work items of such a launch of numFrames frames (no context, no device; request and cache as
+ * irt_debug_void_packets): a launch that renders void packets runs a grid of numFrames rows of
+ * *numLive + *voidPerRow one-wave workgroups, each reading its packet (4 * block + wave) from a list.
+ * items[0 .. *numLive): the live part, the same in every row -- the packets with an active pixel that
+ * are not void, block b's at indices = b mod 8 and consecutive within that residue, the residues padded
+ * to one length with empty items (~0u).  items[*numLive + y * *voidPerRow + k]: void item k of row y --
+ * every void packet once over all rows, ~0u past the last.  Both counts are multiples of 8; packets
+ * without an active pixel are in neither part.  *numVoid: the void packets; 0 (and both counts 0) when
+ * nothing is flagged: such a launch runs the plain grid, and so does one whose rows would not be
+ * shorter than the plain grid's 64 workgroups per tile, or whose kernel has no list form (scenes with
+ * holes).  items NULL: the counts only; else `capacity`
+ * words available, *numLive + numFrames * *voidPerRow needed. */
+int irt_debug_void_lists(irt_debug_void_cache *cache, const irt_launch_params *lp, const irt_volume_info *info,
+                         int W, int H, int tileBegin, int tileStride, const int32_t *tileList, int listCount,
+                         int numFrames, uint32_t *items, size_t capacity, uint32_t *numLive, uint32_t *voidPerRow,
+                         uint32_t *numVoid);
+/* Workgroups the context's last launch dispatched for its raygen (grid x * grid y; 0 for a launch
+ * without tiles); -1 for NULL. */
+long long irt_debug_last_workgroups(const irt_context *ctx);
 /* Chained progressive frames on (default; IRT_CHAIN=0 turns it off per context) or off: a
  * launch of several frames (irt_render_accumulate, irt_render_tiles_accumulate,
  * irt_render_tile_list) lerps each frame straight into accum/fb, frame f's workgroup waiting for

@@ -8,6 +8,13 @@ Workgroup start/end stamps as profiles/wg_trace.py takes them (one-wave workgrou
 each).  The packets are classified here in float64 with no margin (centre direction and largest
 corner angle against the sphere's angular radius), so the figure does not depend on the library's
 own classifier and can be taken on a build without one.  One JSON line per launch.
+
+A launch that runs the void-packet work-item list (Context.last_workgroups differs from the plain
+grid's count) has rows of Lp live and Vr void items instead: its workgroups are decoded through
+irt.void_lists -- workgroup x of row y is live item x, or void item x - Lp of row y; an empty item
+renders nothing -- and the void workgroups are the library's own classification.  Each void packet then
+has one workgroup per launch, in whichever row carries it, so the figure "frames after the first" is
+the void items' lifetime in rows 1 .. B - 1, and the padding's lifetime is reported beside it.
 """
 import argparse
 import json
@@ -56,6 +63,36 @@ def void_packets_f64(cam12, W, H, radius):
     return active & (to_centre - ext > np.arcsin(radius / dist))
 
 
+def report_list_launches(args, ctx, lp, W, H, B, bufs, last, void64):
+    """The launches ran rows of work items (see the head): `last` workgroups each."""
+    live, rows = irt.void_lists(lp, ctx.info, W, H, B)
+    Lp, Vr = live.size, rows.shape[1]
+    assert last == B * (Lp + Vr), (last, B, Lp, Vr)
+    item = np.concatenate([np.broadcast_to(live, (B, Lp)), rows], axis=1).reshape(-1)  # workgroup y (Lp + Vr) + x
+    is_void_part = np.tile(np.arange(Lp + Vr) >= Lp, B)
+    empty = item == 0xFFFFFFFF
+    wg_void = is_void_part & ~empty
+    frame = np.repeat(np.arange(B), Lp + Vr)
+    nvoid = int(np.unique(item[wg_void]).size)
+    for k in range(args.launches):
+        tr = bufs[k].cpu().numpy().view(np.uint32).reshape(-1, 4)[:last]
+        dur = ((tr[:, 1].astype(np.int64) - tr[:, 0].astype(np.int64)) & 0xFFFFFFFF) / 100.0  # us
+        span = ((tr[:, 1].astype(np.int64) - tr[:, 0].astype(np.int64).min()) & 0xFFFFFFFF).max() / 100.0
+        out = {"config": args.config, "launch": k, "frames_per_launch": B, "workgroups": int(last),
+               "plain_grid_workgroups": int(irt.num_tiles(W, H) * 64 * B), "live_items_per_row": int(Lp),
+               "void_items_per_row": int(Vr), "empty_items": int(empty.sum()),
+               "void_packets_per_frame": nvoid, "void_packets_f64": int(void64.sum()),
+               "packets_per_frame": int(irt.num_tiles(W, H) * 64),
+               "void_lifetime_share": round(float(dur[wg_void].sum() / dur.sum()), 4),
+               "void_lifetime_share_frames_after_first": round(float(dur[wg_void & (frame > 0)].sum() / dur.sum()), 4),
+               "empty_item_lifetime_share": round(float(dur[empty].sum() / dur.sum()), 4),
+               "wg_us_mean_void": round(float(dur[wg_void].mean()), 3),
+               "wg_us_mean_empty": round(float(dur[empty].mean()), 3) if empty.any() else None,
+               "wg_us_mean_other": round(float(dur[~is_void_part & ~empty].mean()), 3),
+               "span_us": float(span)}
+        print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c3")
@@ -93,7 +130,12 @@ def main():
         step(args.warmup + k)
     ctx.set_wg_trace(0)
     torch.cuda.synchronize()
+    last = ctx.last_workgroups() if hasattr(irt.lib(), "irt_debug_last_workgroups") else nwg
     void = void_packets_f64(lp.camera12(), W, H, ctx.info.sphericalBounds.upper.x)
+    if last != nwg:
+        report_list_launches(args, ctx, lp, W, H, B, bufs, last, void)
+        ctx.close()
+        return
     # workgroup bx of a frame renders wave (bx >> 3) & 3 of block ((bx >> 5) << 3) | (bx & 7) (k_render)
     bx = np.arange(nt * 64)
     pkt = ((((bx >> 5) << 3) | (bx & 7)) << 2) | ((bx >> 3) & 3)
