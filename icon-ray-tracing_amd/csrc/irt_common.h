@@ -364,6 +364,20 @@ IRT_HD uint32_t cubemap_cell_sub(float px, float py, float pz, int G, uint32_t &
          (uint32_t)(i / kSubCells);
 }
 
+// The points irt_sample_points / irt_sample_latlon hand to a locator (csrc/irt_sample.hip): those
+// whose float squared length, summed as toSpherical's length does (dot3's order), is finite and
+// positive.  Every other point is a miss before any table is indexed: a NaN or infinite
+// coordinate makes the sum NaN or +inf (the squares are never negative, so no inf - inf hides
+// one); so does a finite point whose squares overflow, which the reference misses too (len = inf
+// > height[n]); a sum of 0 (the origin, or squares that underflow) is len = 0 < height[0] on
+// every scene with positive heights.  An admitted point has finite coordinates, a largest
+// magnitude in [2^-76, 2^64) and a finite r = sqrtf(sum) > 0: what the bounds argument of
+// DESIGN.md section 5.11 starts from.
+IRT_HD bool sample_admits(float x, float y, float z) {
+  const float r2 = x * x + y * y + z * z;
+  return r2 > 0.f && r2 < __builtin_inff();
+}
+
 // Per-record height/value block: 64 floats = 256 B, two 128-B lines.
 //   [0..31]  height[0..31]   (ICONCell::height)
 //   [32..62] value[0..30]    (ICONCell::value; value[31] is never read by the render

@@ -215,6 +215,21 @@ struct irt_context {
   long long schedKey[8] = {};
   long long schedSrc = -1;      // launch whose costs the current order came from
   long long schedLastCopy = -1000;
+  // Resampling (irt_sample_points / irt_sample_latlon, irt_sample.hip).  The sampling kernels
+  // only read the scene, so they stay out of the launch ring (no statistics, no chain state);
+  // what must wait for "every launch already issued" also waits for evSample, recorded behind
+  // every sampling kernel (wait_samples).  A sampling call on another stream than the previous
+  // one's first makes its stream wait for that marker, so the newest marker ends them all.
+  hipEvent_t evSample = nullptr;
+  bool samplePending = false;       // evSample is recorded and not yet waited for
+  hipStream_t sampleStream = nullptr;  // stream of the previous sampling call
+  // irt_sample_latlon's tables {cos, sin} x numLat, {cos, sin} x numLon, radius x numLevels: the
+  // device copy the kernel reads and the pinned staging its upload comes from (both grow when a
+  // grid needs more floats); evSampleTab, behind the upload, says when the staging is free again
+  float *d_sampleTab = nullptr, *h_sampleTab = nullptr;
+  size_t sampleTabCap = 0;          // floats in each
+  hipEvent_t evSampleTab = nullptr;
+  bool sampleTabBusy = false;
   // streaming creation (irt_create_begin / _append / _end): the cells and their glibc
   // corner trig go to HBM chunk by chunk; the volume facts, column count and sphere
   // records are folded on the host in record order
@@ -275,3 +290,6 @@ hipError_t wait_slot(irt_context *c, int i);  // waits for the launch in slot i 
 int finish_slot(irt_context *c, int i);       // retires it: its statistics, a chain failure
 int finish_stats(irt_context *c);             // ... every pending launch, oldest first
 int tile_table(irt_context *c, const int32_t *ids, size_t n, int lo, int total, const int32_t **out);
+// irt_sample.hip
+hipError_t wait_samples(irt_context *c);  // waits for every sampling call already issued
+void free_sample_state(irt_context *c);   // after wait_samples: its events, tables and staging

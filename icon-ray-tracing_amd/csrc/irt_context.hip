@@ -38,6 +38,8 @@ namespace {
 void free_all(irt_context *c) {
   if (c->device >= 0) (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
+  (void)wait_samples(c);  // sampling kernels in flight read the arrays freed below
+  free_sample_state(c);
   void *ptrs[] = {c->d_binHdr, c->d_fat, c->slot.slots, c->d_blocks, c->d_sphR, c->d_sphOff, c->d_sphRec,
                   c->d_sphBits, c->d_samples, c->d_maxOp, c->d_gridVR, c->d_gridMaxOp, c->d_gridBits, c->d_wOff, c->d_wRec, c->d_wBox, c->d_wTrig, c->d_schedOrder, c->d_schedCost, c->d_srgb, c->d_valueRanges,
                   c->d_lut, c->d_counters, c->d_counterBuckets, c->d_meta, c->d_queue, c->d_chainFlag,
@@ -692,6 +694,7 @@ int irt_set_transfunc(irt_context *c, const irt_vec4f *lut, int size, irt_box1f 
     const int last = (int)((c->launches - 1) % irt_context::kSlots);
     if (c->ring[last].pending) IRT_HIP(wait_slot(c, last));
   }
+  IRT_HIP(wait_samples(c));  // a sparse transfer function may build the slot table they would read
   if (size > c->lutCap) {
     if (c->d_lut) {
       IRT_HIP(hipStreamSynchronize(c->stream));
@@ -740,6 +743,7 @@ int update_begin(irt_context *c, size_t first, size_t n, const void *values, con
     const int last = (int)((c->launches - 1) % irt_context::kSlots);
     if (c->ring[last].pending) IRT_HIP(wait_slot(c, last));
   }
+  IRT_HIP(wait_samples(c));  // sampling calls count as launches: they read the values
   return IRT_OK;
 }
 // records per staged chunk of a host-pointer update (128 MiB of HBM while the call runs)

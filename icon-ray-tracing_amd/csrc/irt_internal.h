@@ -115,6 +115,14 @@ inline bool update_range_ok(size_t first, size_t n, size_t numCells) {
   return first <= numCells && n <= numCells - first;
 }
 
+// Resampling (host/irt_latlon.cpp; csrc/irt_sample.hip): the most points of one call (2^30 one-wave
+// workgroups: 32 rows of one grid, irt_sample.hip sample_grid), the lat/lon grid's trig rows {cosf, sinf} per
+// latitude and per longitude from the host's glibc, and the grid calls' argument check
+constexpr uint64_t kSampleMaxPoints = uint64_t(1) << 36;
+void latlon_trig(const float *lat, int numLat, const float *lon, int numLon, float *latCS, float *lonCS);
+int latlon_args(const char *what, const float *lat, int numLat, const float *lon, int numLon,
+                const float *radius, int numLevels, size_t *total);
+
 // Measured-cost scheduling (host/irt_sched.cpp): the words of one order buffer from the measured
 // costs of a frame's packets (cost: 4 per 256-pixel block, 64 per 64x64 tile).  out holds
 //   [0, cap)                    the block order: tiles, or bands of max(1, tilesX / tileStride)

@@ -1,0 +1,386 @@
+// irt_sample.hip -- resampling (include/icon_rt_hip.h, "resampling"): the field's value at given
+// points and on a regular lat x lon x level grid, through the raygen's own point location
+// (irt_tracer.h: Tracer::locate_wave for the cell sampler, Tracer<kSamplerVariant>::locate for the
+// wedge and triangle samplers) -- sampleVolume (deviceCode.cu:58-125) without a ray around it.
+// The kernels, their launch and ordering glue, and the two context entry points; the host side
+// (the grid's trig rows, irt_latlon_points, the guard's host compilation) is host/irt_latlon.cpp.
+//
+// The raygen only ever hands the locator points inside the shell; these entry points hand it
+// anything.  admit() below is the guard, and says why every point it lets through indexes every
+// table in bounds.
+
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "irt_build.h"
+#include "irt_context.h"
+#include "irt_tracer.h"
+
+namespace irt {
+
+// What the sampling kernels need beyond RenderArgs (which stays the kernels' FIRST argument:
+// Tracer's late reads go through fresh_args(), the kernarg segment read as a RenderArgs).
+struct SampleArgs {
+  const float *xyz;      // k_sample_points: 3 floats per point
+  const float *latCS;    // k_sample_latlon: {cosf lat, sinf lat} per row ...
+  const float *lonCS;    // ... {cosf lon, sinf lon} per column ...
+  const float *radius;   // ... and the levels' radii
+  int numLat, numLon, numLevels;
+  uint32_t patchesLat, patchesLon;  // 8 x 8 patches per level (the patch form)
+  unsigned long long n;  // points (k_sample_points) or patches (k_sample_latlon)
+  float *value;
+  uint8_t *found;        // may be null
+  float missValue;
+  float rLo, rHi;        // the scene's sphericalBounds.lower.x / upper.x (cell sampler's cut)
+};
+
+namespace {
+
+// The guard.  Returns whether the point goes to the locator.
+//
+// (1) sample_admits (irt_common.h): the squared length is finite and positive.  So the
+//     coordinates are finite, the largest magnitude `den` is a normal float in [2^-76, 2^64),
+//     and r = sqrtf(r2) is finite and positive.  From that, table by table:
+//  - cube-map cell and sub-cell (cubemap_cell_fast, for G and for the wedge locator's wG):
+//    rcpf(den) is finite and normal, |num| <= den, so (num * inv + 1) * fg is finite, in
+//    [0, GS (1 + 2^-22)]; the int conversion is then clamped to [0, GS - 1] in any case, so
+//    cell < 6 G^2 and sub < kSubCells^2 for every float input.  binHdr holds 6 G^2 headers of
+//    kBinHdrWords; wOff holds 6 wG^2 + 1 offsets.
+//  - radial bin (bin_of): three compares, b in [0, 3]; the header's cumulative ends give
+//    [beg, end) inside the cell's own entries by construction of the build.  The second pass
+//    (b + 1, mask shift 8 (b + 1)) runs only when b < kMaxEdges, so the shift is at most 24.
+//  - slot bin (OPT_SLOT): bin_of against slotEdge, whose unused edges are +inf.  r is finite,
+//    so +inf < r is false: b <= the number of finite edges = slotBins - 1.  The slot index is
+//    (cell * units + unit) * slotBins + b with unit < units: inside the table.
+//  - sphere hash: sph_hash(r) >> 18 < 2^14 = 32 kSphBitWords bits, for every float; sphere_at
+//    bisects [0, numSph) and reads sphOff[lo] with lo < numSph.
+//  - candidates, height/value blocks, wedge CSR, boxes and trig: indexed by entry positions and
+//    record numbers the build stored, never by anything computed from the point.
+//  - getValue (record_value, find_value_literal): runs only for a record whose radial test
+//    h0 <= r <= hN passed, as in the raygen; the literal search is bounded by numLayers <= 31.
+//  - locate_tri divides by len = r > 0, finite.
+// (2) the cell sampler's shell cut: r outside [sphericalBounds.lower.x, upper.x] = [min
+//     height[0], max height[numLayers]] fails every record's radial test (ICONGrid.h:184), the
+//     reference's own miss; nothing is read for it.  An empty scene's bounds are (+inf, -inf):
+//     everything is cut.
+template <bool kCell>
+__device__ __forceinline__ bool admit(const SampleArgs &S, float x, float y, float z) {
+  if (!sample_admits(x, y, z)) return false;
+  if constexpr (kCell) {
+    const float r = sqrtf(dot3(x, y, z, x, y, z));  // toSpherical(pos).x, as locate_wave takes it
+    if (!(r >= S.rLo && r <= S.rHi)) return false;
+  }
+  return true;
+}
+
+// One located point's outputs: streaming stores (nobody re-reads them in this kernel), as the
+// raygen's last frame stores its pixels.
+__device__ __forceinline__ void put(const SampleArgs &S, unsigned long long i, bool hit, float v) {
+  __builtin_nontemporal_store(hit ? v : S.missValue, &S.value[i]);
+  if (S.found) __builtin_nontemporal_store((uint8_t)(hit ? 1 : 0), &S.found[i]);
+}
+
+// A one-wave workgroup's LDS: the wave-wide scan's records (cell sampler only) and the Tracer's
+// count words (its serial forms add into them; the forms run here never do)
+template <bool kCell>
+struct SampleLds {
+  CoopWave coop;
+  ScanWave scan;
+  uint32_t cnt[kCnt];
+};
+template <>
+struct SampleLds<false> {
+  uint32_t cnt[kCnt];
+};
+
+// sampleVolume of one wave's 64 points.  `live`: the lane has a point; every lane calls.
+template <int O>
+__device__ __forceinline__ bool wave_locate(const RenderArgs &A, const SampleArgs &S, bool live, float x, float y,
+                                            float z, float &v, SampleLds<(O & OPT_WEDGE) == 0> &L) {
+  constexpr bool kCell = (O & OPT_WEDGE) == 0;
+  const bool want = live && admit<kCell>(S, x, y, z);
+  // the sphere hash from global memory, as the raygen's lean kernels read it
+  Tracer<O> T{{}, A, nullptr, A.sphBits, L.cnt, {0, 0, 0, 0, 0, 0, 0}};
+  if constexpr (kCell) {
+    static_assert(Tracer<O>::kWaveScan, "the cell sampler scans wave-wide");
+    return T.locate_wave(want, x, y, z, v, L.coop, L.scan);
+  } else {
+    return want && T.locate(x, y, z, v);
+  }
+}
+
+// Workgroup w of a sampling grid: one wave each, kGridRow to a grid row (64 kGridRow threads stay
+// below the 2^32 threads a grid's x dimension may hold), the rows in grid y -- at most 32 of them
+// for kSampleMaxPoints points.
+constexpr unsigned long long kGridRow = 1ull << 25;
+__device__ __forceinline__ unsigned long long workgroup_index() {
+  return (unsigned long long)blockIdx.x + kGridRow * (unsigned long long)blockIdx.y;
+}
+inline dim3 sample_grid(unsigned long long wgs) {
+  return dim3((unsigned)std::min(wgs, kGridRow), (unsigned)((wgs + kGridRow - 1) / kGridRow));
+}
+
+// One lane per point, 64 consecutive points per one-wave workgroup.
+template <int O>
+__global__ void __launch_bounds__(64) k_sample_points(RenderArgs A, SampleArgs S) {
+  __shared__ SampleLds<(O & OPT_WEDGE) == 0> L;
+  const unsigned long long w = workgroup_index();
+  if (w * 64ull >= S.n) return;  // wave-uniform (the last grid row's tail)
+  const unsigned long long i = w * 64ull + threadIdx.x;
+  const bool live = i < S.n;
+  float x = 0.f, y = 0.f, z = 0.f;
+  if (live) {
+    x = S.xyz[3 * i];
+    y = S.xyz[3 * i + 1];
+    z = S.xyz[3 * i + 2];
+  }
+  float v = 0.f;
+  const bool hit = wave_locate<O>(A, S, live, x, y, z, v, L);
+  if (live) put(S, i, hit, v);
+}
+
+// The lat x lon x level grid, its points made from the three tables exactly as
+// to_cartesian_trig (irt_build.h) makes them; no xyz array exists.  A wave takes an 8 x 8
+// lat x lon patch of one level (lane = 8 * dlat + dlon), the shape of the raygen's packet:
+// neighbouring lanes share header lines, fat entries and height/value blocks.  S.n = patches;
+// patch w = (level, patch row, patch column).
+template <int O>
+__global__ void __launch_bounds__(64) k_sample_latlon(RenderArgs A, SampleArgs S) {
+  __shared__ SampleLds<(O & OPT_WEDGE) == 0> L;
+  const unsigned long long w = workgroup_index();
+  if (w >= S.n) return;  // wave-uniform
+  const unsigned long long perLevel = (unsigned long long)S.patchesLat * S.patchesLon;
+  const unsigned long long k = w / perLevel;  // < numLevels: w < S.n = numLevels * perLevel
+  const unsigned long long q = w - k * perLevel;
+  const unsigned long long j = (q / S.patchesLon) * 8ull + (threadIdx.x >> 3);
+  const unsigned long long i = (q % S.patchesLon) * 8ull + (threadIdx.x & 7u);
+  // live lanes index the tables inside their sizes: j < numLat, i < numLon
+  const bool live = j < (unsigned long long)S.numLat && i < (unsigned long long)S.numLon;
+  float x = 0.f, y = 0.f, z = 0.f;
+  if (live) {
+    const float r = S.radius[k];
+    const float t[4] = {S.latCS[2 * j], S.latCS[2 * j + 1], S.lonCS[2 * i], S.lonCS[2 * i + 1]};
+    to_cartesian_trig(r, t, x, y, z);
+  }
+  float v = 0.f;
+  const bool hit = wave_locate<O>(A, S, live, x, y, z, v, L);
+  if (live) put(S, (k * (unsigned long long)S.numLat + j) * (unsigned long long)S.numLon + i, hit, v);
+}
+
+// the cell sampler's Tracer, as k_debug_locate_wave instantiates it: from headers (with the
+// quad-bound miss test), or from the slot table where the context's frames start there
+constexpr int kCellVariant = kDefaultVariant & ~OPT_MONO;
+
+template <int O>
+void launch_points(const RenderArgs &A, const SampleArgs &S, hipStream_t s) {
+  hipLaunchKernelGGL(k_sample_points<O>, sample_grid((S.n + 63ull) / 64ull), dim3(64), 0, s, A, S);
+}
+template <int O>
+void launch_latlon(const RenderArgs &A, const SampleArgs &S, hipStream_t s) {
+  hipLaunchKernelGGL(k_sample_latlon<O>, sample_grid(S.n), dim3(64), 0, s, A, S);
+}
+
+// The scene side of a sampling launch's arguments (what debug_locate* fill for the hooks)
+void scene_args(const irt_context *c, int mode, RenderArgs &A) {
+  memset(&A, 0, sizeof(A));
+  A.numCells = c->n;
+  A.sampler = mode;
+  A.blocks = c->d_blocks;
+  if (mode == IRT_MODE_USER_GEOM) {
+    A.G = c->G;
+    A.binHdr = c->d_binHdr;
+    A.fat = c->d_fat;
+    A.slots = c->slotAlways || c->slotSparse ? c->slot.slots : nullptr;  // as the frames (launch_args)
+    A.slotBins = c->slot.bins;
+    A.slotSubs = c->slot.subs;
+    for (int k = 0; k < 3; ++k) A.slotEdge[k] = c->slot.edges[k];
+    A.numSph = c->numSph;
+    A.sphR = c->d_sphR;
+    A.sphOff = c->d_sphOff;
+    A.sphRec = c->d_sphRec;
+    A.sphBits = c->d_sphBits;
+  } else {
+    A.wG = c->wG;
+    A.wOff = c->d_wOff;
+    A.wRec = c->d_wRec;
+    A.wBox = c->d_wBox;
+    A.wTrig = c->d_wTrig;
+  }
+}
+
+// The checks every sampling call makes before it touches the device
+int sample_check(const irt_context *c, int mode, const char *what) {
+  if (!c || c->building) {
+    set_error("%s: null context, or a context still being created", what);
+    return IRT_E_INVALID;
+  }
+  if (mode != IRT_MODE_USER_GEOM && mode != IRT_MODE_CUBQL && mode != IRT_MODE_TRIANGLES) {
+    set_error("%s: sampler mode %d is none of IRT_MODE_USER_GEOM, IRT_MODE_CUBQL, IRT_MODE_TRIANGLES", what,
+              mode);
+    return IRT_E_INVALID;
+  }
+  if (c->updPending) return update_pending(what);
+  if (mode != IRT_MODE_USER_GEOM && c->wG == 0 && c->n != 0) {  // (an empty scene has nothing to list)
+    set_error("%s: sampler mode %d needs irt_build_wedge_accel first", what, mode);
+    return IRT_E_INVALID;
+  }
+  return IRT_OK;
+}
+
+// Before a sampling call queues anything on `s`: its place behind the previous sampling call
+int sample_begin(irt_context *c, hipStream_t s) {
+  IRT_HIP(hipSetDevice(c->device));
+  if (!c->evSample) IRT_HIP(hipEventCreateWithFlags(&c->evSample, hipEventDisableTiming));
+  if (c->samplePending && s != c->sampleStream) IRT_HIP(hipStreamWaitEvent(s, c->evSample, 0));
+  c->sampleStream = s;
+  return IRT_OK;
+}
+// ... and after its kernel
+int sample_end(irt_context *c, hipStream_t s) {
+  IRT_HIP(hipGetLastError());
+  IRT_HIP(hipEventRecord(c->evSample, s));
+  c->samplePending = true;
+  return IRT_OK;
+}
+
+void launch_sample(const irt_context *c, int mode, const RenderArgs &A, const SampleArgs &S, bool latlon,
+                   hipStream_t s) {
+  if (mode != IRT_MODE_USER_GEOM) {
+    latlon ? launch_latlon<kSamplerVariant>(A, S, s) : launch_points<kSamplerVariant>(A, S, s);
+  } else if (A.slots) {
+    latlon ? launch_latlon<kCellVariant | OPT_SLOT>(A, S, s) : launch_points<kCellVariant | OPT_SLOT>(A, S, s);
+  } else {
+    latlon ? launch_latlon<kCellVariant>(A, S, s) : launch_points<kCellVariant>(A, S, s);
+  }
+}
+
+}  // namespace
+}  // namespace irt
+
+using namespace irt;
+
+hipError_t wait_samples(irt_context *c) {
+  if (!c->samplePending) return hipSuccess;
+  const hipError_t e = hipEventSynchronize(c->evSample);
+  if (e == hipSuccess) c->samplePending = false;
+  return e;
+}
+
+void free_sample_state(irt_context *c) {
+  if (c->sampleTabBusy) (void)hipEventSynchronize(c->evSampleTab);
+  if (c->d_sampleTab) (void)hipFree(c->d_sampleTab);
+  if (c->h_sampleTab) (void)hipHostFree(c->h_sampleTab);
+  if (c->evSample) (void)hipEventDestroy(c->evSample);
+  if (c->evSampleTab) (void)hipEventDestroy(c->evSampleTab);
+  c->d_sampleTab = c->h_sampleTab = nullptr;
+  c->evSample = c->evSampleTab = nullptr;
+  c->sampleTabCap = 0;
+  c->samplePending = c->sampleTabBusy = false;
+}
+
+extern "C" {
+
+int irt_sample_points(irt_context *c, int mode, const float *d_xyz, size_t n, float *d_value, uint8_t *d_found,
+                      float missValue, void *stream) {
+  int rc = sample_check(c, mode, "irt_sample_points");
+  if (rc) return rc;
+  if ((uint64_t)n > kSampleMaxPoints) {
+    set_error("irt_sample_points: %zu points are more than 2^36 (or a negative count)", n);
+    return IRT_E_INVALID;
+  }
+  if (n && (!d_xyz || !d_value)) {
+    set_error("irt_sample_points: null d_xyz or d_value");
+    return IRT_E_INVALID;
+  }
+  if (n == 0) return IRT_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = sample_begin(c, s))) return rc;
+  RenderArgs A;
+  scene_args(c, mode, A);
+  SampleArgs S;
+  memset(&S, 0, sizeof(S));
+  S.xyz = d_xyz;
+  S.n = n;
+  S.value = d_value;
+  S.found = d_found;
+  S.missValue = missValue;
+  S.rLo = c->info.sphericalBounds.lower.x;
+  S.rHi = c->info.sphericalBounds.upper.x;
+  launch_sample(c, mode, A, S, false, s);
+  return sample_end(c, s);
+}
+
+int irt_sample_latlon(irt_context *c, int mode, const float *lat, int numLat, const float *lon, int numLon,
+                      const float *radius, int numLevels, float *d_value, uint8_t *d_found, float missValue,
+                      void *stream) {
+  int rc = sample_check(c, mode, "irt_sample_latlon");
+  if (rc) return rc;
+  size_t total = 0;
+  if ((rc = latlon_args("irt_sample_latlon", lat, numLat, lon, numLon, radius, numLevels, &total))) return rc;
+  if (total && !d_value) {
+    set_error("irt_sample_latlon: null d_value");
+    return IRT_E_INVALID;
+  }
+  if (total == 0) return IRT_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = sample_begin(c, s))) return rc;
+  // the tables: through the context's pinned staging into its device copy, both grown on demand
+  const size_t need = 2 * (size_t)numLat + 2 * (size_t)numLon + (size_t)numLevels;
+  if (!c->evSampleTab) IRT_HIP(hipEventCreateWithFlags(&c->evSampleTab, hipEventDisableTiming));
+  if (c->sampleTabBusy) {  // the previous call's upload still reads the staging
+    IRT_HIP(hipEventSynchronize(c->evSampleTab));
+    c->sampleTabBusy = false;
+  }
+  if (need > c->sampleTabCap) {
+    IRT_HIP(wait_samples(c));  // an earlier grid's kernel may still read the device copy
+    if (c->d_sampleTab) {
+      IRT_HIP(hipFree(c->d_sampleTab));
+      c->d_sampleTab = nullptr;
+      c->bytes -= c->sampleTabCap * sizeof(float);
+    }
+    if (c->h_sampleTab) {
+      IRT_HIP(hipHostFree(c->h_sampleTab));
+      c->h_sampleTab = nullptr;
+    }
+    c->sampleTabCap = 0;
+    c->info.deviceBytes = c->bytes;
+    const size_t cap = std::max<size_t>(need + need / 2, 4096);
+    IRT_HIP(hipHostMalloc((void **)&c->h_sampleTab, cap * sizeof(float)));
+    if ((rc = dalloc(c, &c->d_sampleTab, cap))) return rc;  // (the staging stays, with capacity 0: the next
+                                                            // call frees it and allocates both anew)
+    c->sampleTabCap = cap;
+    c->info.deviceBytes = c->bytes;
+  }
+  float *latCS = c->h_sampleTab, *lonCS = latCS + 2 * (size_t)numLat, *rad = lonCS + 2 * (size_t)numLon;
+  latlon_trig(lat, numLat, lon, numLon, latCS, lonCS);
+  memcpy(rad, radius, (size_t)numLevels * sizeof(float));
+  // behind every earlier sampling kernel (same stream: stream order; another: sample_begin's wait)
+  IRT_HIP(hipMemcpyAsync(c->d_sampleTab, c->h_sampleTab, need * sizeof(float), hipMemcpyHostToDevice, s));
+  IRT_HIP(hipEventRecord(c->evSampleTab, s));
+  c->sampleTabBusy = true;
+
+  RenderArgs A;
+  scene_args(c, mode, A);
+  SampleArgs S;
+  memset(&S, 0, sizeof(S));
+  S.latCS = c->d_sampleTab;
+  S.lonCS = S.latCS + 2 * (size_t)numLat;
+  S.radius = S.lonCS + 2 * (size_t)numLon;
+  S.numLat = numLat;
+  S.numLon = numLon;
+  S.numLevels = numLevels;
+  S.patchesLat = ((uint32_t)numLat + 7u) / 8u;
+  S.patchesLon = ((uint32_t)numLon + 7u) / 8u;
+  S.n = (unsigned long long)numLevels * S.patchesLat * S.patchesLon;
+  S.value = d_value;
+  S.found = d_found;
+  S.missValue = missValue;
+  S.rLo = c->info.sphericalBounds.lower.x;
+  S.rHi = c->info.sphericalBounds.upper.x;
+  launch_sample(c, mode, A, S, true, s);
+  return sample_end(c, s);
+}
+
+}  // extern "C"

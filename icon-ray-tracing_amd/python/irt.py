@@ -149,6 +149,10 @@ def lib() -> C.CDLL:
             "irt_update_values": [P, S, S, P],
             "irt_update_values_device": [P, S, S, P, P],
             "irt_update_values_end": [P],
+            "irt_sample_points": [P, I, P, S, P, P, F, P],
+            "irt_sample_latlon": [P, I, P, I, P, I, P, I, P, P, F, P],
+            "irt_latlon_points": [P, I, P, I, P, I, P],
+            "irt_debug_sample_admits": [F, F, F],
             "irt_clear_frame": [P, P, P, S, P],
             "irt_render": [P, C.POINTER(LaunchParams), I, I, P, P, P],
             "irt_render_tiles": [P, C.POINTER(LaunchParams), I, I, I, I, P, P,
@@ -354,6 +358,27 @@ def filter_cells(cells: np.ndarray, lat_range=(-np.inf, np.inf), lon_range=(-np.
     _check(lib().irt_filter_cells(_ptr(out), out.size, box1(*lat_range), box1(*lon_range),
                                   C.byref(n)), "irt_filter_cells")
     return out[: n.value].copy()
+
+
+def _latlon_arrays(lat, lon, radius):
+    return tuple(np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (lat, lon, radius))
+
+
+def latlon_points(lat, lon, radius) -> np.ndarray:
+    """irt_latlon_points: the points Context.sample_latlon samples, float32 of shape
+    (len(radius), len(lat), len(lon), 3): toCartesian(radius[k], lat[j], lon[i]) with the host's
+    cosf/sinf (lat/lon in radians, radius in metres from the Earth's centre).  No GPU."""
+    lat, lon, radius = _latlon_arrays(lat, lon, radius)
+    xyz = np.zeros((radius.size, lat.size, lon.size, 3), np.float32)
+    _check(lib().irt_latlon_points(_ptr(lat), lat.size, _ptr(lon), lon.size, _ptr(radius),
+                                   radius.size, _ptr(xyz)), "irt_latlon_points")
+    return xyz
+
+
+def sample_admits(x: float, y: float, z: float) -> bool:
+    """irt_debug_sample_admits: whether the sampling calls hand the point to a locator (its
+    float squared length is finite and positive); every other point is a miss by definition."""
+    return lib().irt_debug_sample_admits(C.c_float(x), C.c_float(y), C.c_float(z)) == 1
 
 
 def volume_info(cells: np.ndarray) -> VolumeInfo:
@@ -854,6 +879,48 @@ class Context:
         cells = np.ascontiguousarray(cells, dtype=CELL_DTYPE)
         _check(lib().irt_build_wedge_accel(self._h, _ptr(cells), cells.size),
                "irt_build_wedge_accel")
+
+    def sample_points(self, xyz_ptr: int, n: int, value_ptr: int, found_ptr: int = 0,
+                      mode: int = MODE_USER_GEOM, miss: float = float("nan"), stream: int = 0):
+        """irt_sample_points: value[i] = the `mode` sampler's value at point i of n x 3 float32 in
+        device memory at xyz_ptr, or `miss` where no cell holds it; found[i] = 1/0 (uint8;
+        found_ptr 0: not written).  Device pointers, enqueued on `stream`."""
+        _check(lib().irt_sample_points(self._h, int(mode), C.c_void_p(xyz_ptr), int(n),
+                                       C.c_void_p(value_ptr), C.c_void_p(found_ptr), float(miss),
+                                       C.c_void_p(stream)), "irt_sample_points")
+
+    def sample_latlon(self, lat, lon, radius, value_ptr: int, found_ptr: int = 0,
+                      mode: int = MODE_USER_GEOM, miss: float = float("nan"), stream: int = 0):
+        """irt_sample_latlon: the same on the grid latlon_points(lat, lon, radius) (host arrays,
+        radians and metres from the centre), value at [(k * len(lat) + j) * len(lon) + i] of the
+        device arrays; no point array exists.  Returns the grid's shape (levels, lat, lon)."""
+        lat, lon, radius = _latlon_arrays(lat, lon, radius)
+        _check(lib().irt_sample_latlon(self._h, int(mode), _ptr(lat), lat.size, _ptr(lon), lon.size,
+                                       _ptr(radius), radius.size, C.c_void_p(value_ptr),
+                                       C.c_void_p(found_ptr), float(miss), C.c_void_p(stream)),
+               "irt_sample_latlon")
+        return radius.size, lat.size, lon.size
+
+    def resample(self, points, mode: int = MODE_USER_GEOM, miss: float = float("nan")):
+        """The field at `points` (..., 3): a float32 torch tensor on the context's device (sampled
+        in place, on torch's current stream) or a numpy array (which goes up and comes back).
+        Returns (value float32, found bool) of shape points.shape[:-1], of the same kind."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        host = not isinstance(points, torch.Tensor)
+        pts = torch.from_numpy(np.array(points, dtype=np.float32, order="C")).to(dev) if host else points
+        if pts.device != dev or pts.dtype != torch.float32 or pts.shape[-1] != 3:
+            raise IrtError(f"resample: points must be float32 (..., 3) on {dev}, got {pts.dtype} "
+                           f"{tuple(pts.shape)} on {pts.device}")
+        with torch.cuda.device(dev):
+            pts = pts.contiguous()
+            value = torch.empty(pts.shape[:-1], dtype=torch.float32, device=dev)
+            found = torch.empty(pts.shape[:-1], dtype=torch.uint8, device=dev)
+            self.sample_points(pts.data_ptr(), value.numel(), value.data_ptr(), found.data_ptr(), mode,
+                               miss, torch.cuda.current_stream(dev).cuda_stream)
+            if host:
+                return value.cpu().numpy(), found.cpu().numpy().astype(bool)
+        return value, found.bool()
 
     def locate_sampler(self, points: np.ndarray, mode: int) -> tuple[np.ndarray, np.ndarray]:
         """irt_debug_locate_sampler: the device point location of the MODE_CUBQL or

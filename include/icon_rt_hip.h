@@ -200,6 +200,46 @@ int irt_update_values_device(irt_context *ctx, size_t first, size_t n, const flo
  * nothing pending: IRT_OK, nothing done. */
 int irt_update_values_end(irt_context *ctx);
 
+/* ---------------------------------------------------------------- resampling
+ * The field's value at points, or on a regular lat x lon x level grid, through the raygen's own
+ * point location: sampleVolume (deviceCode.cu:58-125) of the chosen sampler without a ray around
+ * it.  No counterpart in the reference, whose only consumer of sampleVolume is the raygen.
+ *  - mode: IRT_MODE_USER_GEOM, IRT_MODE_CUBQL or IRT_MODE_TRIANGLES; the last two need
+ *    irt_build_wedge_accel (IRT_E_INVALID without it).
+ *  - d_xyz, d_value, d_found: DEVICE pointers on the context's device, used on `stream`; they must
+ *    stay valid until that work has run.  d_found may be NULL.
+ *  - Points that are never located (a miss, found = 0): a point with a non-finite coordinate (a
+ *    documented deviation: the reference's sample() has no defined answer for NaN), and a point
+ *    whose float squared length x*x + y*y + z*z is not finite and positive (the reference's own
+ *    answer on every scene whose heights are positive: len < height[0] or len > height[n]).
+ *  - Ordering: a sampling call counts as a launch of the context for everything that waits for
+ *    every launch already issued (irt_update_values*, irt_set_transfunc, irt_destroy); sampling
+ *    calls after irt_update_values_end see the committed values; between the first
+ *    irt_update_values* and irt_update_values_end they return IRT_E_INVALID as irt_render does.
+ *    They touch neither the render statistics nor fb/accum, and neither report nor consume
+ *    IRT_E_CHAIN.  Sampling calls of one context run in call order, whatever their streams.
+ *  - IRT_E_INVALID, nothing written: a NULL or still-building context, a bad mode, NULL d_xyz or
+ *    d_value with points to sample, a negative count, more than 2^36 points.  Zero points:
+ *    IRT_OK, nothing launched.
+ *  - No record index is returned (the raygen's locator yields none).
+ *
+ * value[i] = the sampler's value at point i (xyz[3i .. 3i+2]) or missValue where no cell holds
+ * it; found[i] = 1/0. */
+int irt_sample_points(irt_context *ctx, int mode, const float *d_xyz, size_t n, float *d_value,
+                      uint8_t *d_found, float missValue, void *stream);
+/* The regular grid: point (k, j, i) = toCartesian(radius[k], lat[j], lon[i]) (ICONGrid.h:44-54:
+ * x = (r cos lat) cos lon, y = (r cos lat) sin lon, z = r sin lat, cosf/sinf from the host's
+ * glibc once per row and per column, so every point has the bits of the reference's
+ * toCartesian), its value at d_value[(k*numLat + j)*numLon + i].  lat/lon in radians, radius in
+ * metres from the Earth's centre; HOST arrays, copied before the call returns.  Equal, bit for
+ * bit, to irt_sample_points on irt_latlon_points' output. */
+int irt_sample_latlon(irt_context *ctx, int mode, const float *lat, int numLat, const float *lon,
+                      int numLon, const float *radius, int numLevels, float *d_value,
+                      uint8_t *d_found, float missValue, void *stream);
+/* Host helper, no GPU: the points irt_sample_latlon samples, xyz[3*((k*numLat + j)*numLon + i) ...]. */
+int irt_latlon_points(const float *lat, int numLat, const float *lon, int numLon,
+                      const float *radius, int numLevels, float *xyz);
+
 /* == clearFramebuffer (common/pipeline.cu:171-199): fb = make_rgba(0), accum = 0. */
 int irt_clear_frame(irt_context *ctx, uint32_t *d_fb, irt_vec4f *d_accum, size_t numPixels,
                     void *stream);

@@ -156,6 +156,11 @@ int irt_debug_locate_wave(irt_context *ctx, const float *xyz, int n, int *found,
  * irt_build_wedge_accel, or while a value update is pending, as irt_render; n == 0 is IRT_OK. */
 int irt_debug_locate_sampler(irt_context *ctx, int mode, const float *xyz, int n, int *found,
                              float *value);
+/* The guard of irt_sample_points / irt_sample_latlon (irt_common.h sample_admits), compiled for
+ * the host: 1 when the point goes to a locator -- its float squared length x*x + y*y + z*z is
+ * finite and positive --, 0 when it is a miss by definition (a NaN or infinite coordinate, the
+ * origin, squares that overflow or underflow to 0). */
+int irt_debug_sample_admits(float x, float y, float z);
 /* Measured-cost scheduling state: the policy (IRT_SCHED; 0 = off), whether the last launch
  * ran its workgroups in a measured-cost order, and how many launches have. */
 int irt_debug_sched(irt_context *ctx, int *policy, int *lastApplied, long long *applied);
