@@ -293,3 +293,19 @@ int tile_table(irt_context *c, const int32_t *ids, size_t n, int lo, int total, 
 // irt_sample.hip
 hipError_t wait_samples(irt_context *c);  // waits for every sampling call already issued
 void free_sample_state(irt_context *c);   // after wait_samples: its events, tables and staging
+
+namespace irt {
+// irt_launch.hip: what a frame's RenderArgs takes from the launch parameters, the transfer function
+// and the caller's buffers -- the camera, accumID and its lerp weight, the ambient terms, the
+// classification and the pixel write -- as every render launch fills them (fill_args)
+void frame_args(const irt_context *c, const irt_launch_params *lp, uint32_t *fb, irt_vec4f *accum, RenderArgs &A);
+// irt_sample.hip: what the sampling calls (irt_sample.hip, irt_levels.hip) share on the host.
+// scene_args zeroes A and fills the scene side of a sampling launch's arguments; sample_check is
+// the checks every sampling call makes before it touches the device; sample_begin takes the call's
+// place behind the previous sampling call before anything is queued on `s`, sample_end marks its
+// kernel's end
+void scene_args(const irt_context *c, int mode, RenderArgs &A);
+int sample_check(const irt_context *c, int mode, const char *what);
+int sample_begin(irt_context *c, hipStream_t s);
+int sample_end(irt_context *c, hipStream_t s);
+}  // namespace irt

@@ -123,6 +123,12 @@ void latlon_trig(const float *lat, int numLat, const float *lon, int numLon, flo
 int latlon_args(const char *what, const float *lat, int numLat, const float *lon, int numLon,
                 const float *radius, int numLevels, size_t *total);
 
+// Level surfaces (host/irt_level_order.cpp; csrc/irt_levels.hip): the check of the radii
+// (numLevels in [1, IRT_MAX_LEVELS], every radius finite and positive), and the near order of the
+// hit slots -- sorted[h] = radius[index[h]], descending, ties by ascending index
+int levels_args(const char *what, const float *radius, int numLevels);
+void levels_order(const float *radius, int numLevels, float *sorted, int32_t *index);
+
 // Measured-cost scheduling (host/irt_sched.cpp): the words of one order buffer from the measured
 // costs of a frame's packets (cost: 4 per 256-pixel block, 64 per 64x64 tile).  out holds
 //   [0, cap)                    the block order: tiles, or bands of max(1, tilesX / tileStride)

@@ -137,6 +137,31 @@ int finish_stats(irt_context *c) {
   return IRT_OK;
 }
 
+// The frame side of RenderArgs (irt_context.h): shared by every render launch (fill_args) and by
+// irt_render_levels (irt_levels.hip), whose kernel runs the raygen's gen_ray, post_classify and
+// write_pixel on it
+void irt::frame_args(const irt_context *c, const irt_launch_params *lp, uint32_t *fb, irt_vec4f *accum,
+                     RenderArgs &A) {
+  A.org = make_float3(lp->org.x, lp->org.y, lp->org.z);
+  A.dir00 = make_float3(lp->dir_00.x, lp->dir_00.y, lp->dir_00.z);
+  A.du = make_float3(lp->dir_du.x, lp->dir_du.y, lp->dir_du.z);
+  A.dv = make_float3(lp->dir_dv.x, lp->dir_dv.y, lp->dir_dv.z);
+  A.accumID = lp->accumID;
+  A.accumW = 1.f / (float)(lp->accumID + 1);  // the lerp weight (deviceCode.cu:333), per launch
+  A.amb = make_float3(lp->ambientColor.x, lp->ambientColor.y, lp->ambientColor.z);
+  A.ambRad = lp->ambientRadiance;
+  A.tfLo = c->tfLo;
+  A.tfHi = c->tfHi;
+  const float tfSize = c->tfHi - c->tfLo;  // float, as the reference subtracts
+  A.invTf = 1.0 / (double)tfSize;
+  A.opacityScale = c->opScale;
+  A.lut = c->d_lut;
+  A.lutSize = c->lutSize;
+  A.srgbTh = c->d_srgb;
+  A.fb = fb;
+  A.accum = (float4 *)accum;
+}
+
 namespace {
 
 // ---------------------------------------------------------------- buffer growth
@@ -356,14 +381,7 @@ int resolve_tiles(irt_context *c, const RenderRequest &r, Launch &L) {
 // the camera and scene fields of RenderArgs
 void fill_args(const irt_context *c, const irt_launch_params *lp, uint32_t *fb, irt_vec4f *accum, Launch &L) {
   RenderArgs &A = L.A;
-  A.org = make_float3(lp->org.x, lp->org.y, lp->org.z);
-  A.dir00 = make_float3(lp->dir_00.x, lp->dir_00.y, lp->dir_00.z);
-  A.du = make_float3(lp->dir_du.x, lp->dir_du.y, lp->dir_du.z);
-  A.dv = make_float3(lp->dir_dv.x, lp->dir_dv.y, lp->dir_dv.z);
-  A.accumID = lp->accumID;
-  A.accumW = 1.f / (float)(lp->accumID + 1);  // the lerp weight (deviceCode.cu:333), per launch
-  A.amb = make_float3(lp->ambientColor.x, lp->ambientColor.y, lp->ambientColor.z);
-  A.ambRad = lp->ambientRadiance;
+  frame_args(c, lp, fb, accum, A);
   A.unitDistance = lp->unitDistance;
   A.raygen = lp->raygen;
   const irt_volume_info &I = c->info;
@@ -382,28 +400,18 @@ void fill_args(const irt_context *c, const irt_launch_params *lp, uint32_t *fb, 
   A.wRec = c->d_wRec;
   A.wBox = c->d_wBox;
   A.wTrig = c->d_wTrig;
-  A.tfLo = c->tfLo;
-  A.tfHi = c->tfHi;
   {
-    const float tfSize = c->tfHi - c->tfLo;  // float, as the reference subtracts
-    A.invTf = 1.0 / (double)tfSize;
     const float sz[3] = {I.sphericalBounds.upper.x - I.sphericalBounds.lower.x,
                          I.sphericalBounds.upper.y - I.sphericalBounds.lower.y,
                          I.sphericalBounds.upper.z - I.sphericalBounds.lower.z};
     for (int k = 0; k < 3; ++k) A.invSb[k] = 1.0 / (double)sz[k];
   }
-  A.opacityScale = c->opScale;
-  A.lut = c->d_lut;
-  A.lutSize = c->lutSize;
   A.coopMaxLg = c->coopMaxLg;
   A.coopRamp = c->coopRamp;
   A.probeExit = c->probeExit;
   A.wgTrace = c->wgTrace;
   A.numCells = c->n;
   A.G = c->G;
-  A.srgbTh = c->d_srgb;
-  A.fb = fb;
-  A.accum = (float4 *)accum;
   A.counters = c->d_counters + 16 * L.slot;
   A.binHdr = c->d_binHdr;
   A.fat = c->d_fat;

@@ -5,9 +5,9 @@
 // The kernels, their launch and ordering glue, and the two context entry points; the host side
 // (the grid's trig rows, irt_latlon_points, the guard's host compilation) is host/irt_latlon.cpp.
 //
-// The raygen only ever hands the locator points inside the shell; these entry points hand it
-// anything.  admit() below is the guard, and says why every point it lets through indexes every
-// table in bounds.
+// The guard in front of the locator (admit) and sampleVolume of a wave's points (wave_locate) are
+// in irt_sample_dev.h, which irt_levels.hip shares; so are this file's scene_args, sample_check,
+// sample_begin and sample_end (declared in irt_context.h).
 
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -16,7 +16,7 @@
 
 #include "irt_build.h"
 #include "irt_context.h"
-#include "irt_tracer.h"
+#include "irt_sample_dev.h"
 
 namespace irt {
 
@@ -35,152 +35,6 @@ struct SampleArgs {
   float missValue;
   float rLo, rHi;        // the scene's sphericalBounds.lower.x / upper.x (cell sampler's cut)
 };
-
-namespace {
-
-// The guard.  Returns whether the point goes to the locator.
-//
-// (1) sample_admits (irt_common.h): the squared length is finite and positive.  So the
-//     coordinates are finite, the largest magnitude `den` is a normal float in [2^-76, 2^64),
-//     and r = sqrtf(r2) is finite and positive.  From that, table by table:
-//  - cube-map cell and sub-cell (cubemap_cell_fast, for G and for the wedge locator's wG):
-//    rcpf(den) is finite and normal, |num| <= den, so (num * inv + 1) * fg is finite, in
-//    [0, GS (1 + 2^-22)]; the int conversion is then clamped to [0, GS - 1] in any case, so
-//    cell < 6 G^2 and sub < kSubCells^2 for every float input.  binHdr holds 6 G^2 headers of
-//    kBinHdrWords; wOff holds 6 wG^2 + 1 offsets.
-//  - radial bin (bin_of): three compares, b in [0, 3]; the header's cumulative ends give
-//    [beg, end) inside the cell's own entries by construction of the build.  The second pass
-//    (b + 1, mask shift 8 (b + 1)) runs only when b < kMaxEdges, so the shift is at most 24.
-//  - slot bin (OPT_SLOT): bin_of against slotEdge, whose unused edges are +inf.  r is finite,
-//    so +inf < r is false: b <= the number of finite edges = slotBins - 1.  The slot index is
-//    (cell * units + unit) * slotBins + b with unit < units: inside the table.
-//  - sphere hash: sph_hash(r) >> 18 < 2^14 = 32 kSphBitWords bits, for every float; sphere_at
-//    bisects [0, numSph) and reads sphOff[lo] with lo < numSph.
-//  - candidates, height/value blocks, wedge CSR, boxes and trig: indexed by entry positions and
-//    record numbers the build stored, never by anything computed from the point.
-//  - getValue (record_value, find_value_literal): runs only for a record whose radial test
-//    h0 <= r <= hN passed, as in the raygen; the literal search is bounded by numLayers <= 31.
-//  - locate_tri divides by len = r > 0, finite.
-// (2) the cell sampler's shell cut: r outside [sphericalBounds.lower.x, upper.x] = [min
-//     height[0], max height[numLayers]] fails every record's radial test (ICONGrid.h:184), the
-//     reference's own miss; nothing is read for it.  An empty scene's bounds are (+inf, -inf):
-//     everything is cut.
-template <bool kCell>
-__device__ __forceinline__ bool admit(const SampleArgs &S, float x, float y, float z) {
-  if (!sample_admits(x, y, z)) return false;
-  if constexpr (kCell) {
-    const float r = sqrtf(dot3(x, y, z, x, y, z));  // toSpherical(pos).x, as locate_wave takes it
-    if (!(r >= S.rLo && r <= S.rHi)) return false;
-  }
-  return true;
-}
-
-// One located point's outputs: streaming stores (nobody re-reads them in this kernel), as the
-// raygen's last frame stores its pixels.
-__device__ __forceinline__ void put(const SampleArgs &S, unsigned long long i, bool hit, float v) {
-  __builtin_nontemporal_store(hit ? v : S.missValue, &S.value[i]);
-  if (S.found) __builtin_nontemporal_store((uint8_t)(hit ? 1 : 0), &S.found[i]);
-}
-
-// A one-wave workgroup's LDS: the wave-wide scan's records (cell sampler only) and the Tracer's
-// count words (its serial forms add into them; the forms run here never do)
-template <bool kCell>
-struct SampleLds {
-  CoopWave coop;
-  ScanWave scan;
-  uint32_t cnt[kCnt];
-};
-template <>
-struct SampleLds<false> {
-  uint32_t cnt[kCnt];
-};
-
-// sampleVolume of one wave's 64 points.  `live`: the lane has a point; every lane calls.
-template <int O>
-__device__ __forceinline__ bool wave_locate(const RenderArgs &A, const SampleArgs &S, bool live, float x, float y,
-                                            float z, float &v, SampleLds<(O & OPT_WEDGE) == 0> &L) {
-  constexpr bool kCell = (O & OPT_WEDGE) == 0;
-  const bool want = live && admit<kCell>(S, x, y, z);
-  // the sphere hash from global memory, as the raygen's lean kernels read it
-  Tracer<O> T{{}, A, nullptr, A.sphBits, L.cnt, {0, 0, 0, 0, 0, 0, 0}};
-  if constexpr (kCell) {
-    static_assert(Tracer<O>::kWaveScan, "the cell sampler scans wave-wide");
-    return T.locate_wave(want, x, y, z, v, L.coop, L.scan);
-  } else {
-    return want && T.locate(x, y, z, v);
-  }
-}
-
-// Workgroup w of a sampling grid: one wave each, kGridRow to a grid row (64 kGridRow threads stay
-// below the 2^32 threads a grid's x dimension may hold), the rows in grid y -- at most 32 of them
-// for kSampleMaxPoints points.
-constexpr unsigned long long kGridRow = 1ull << 25;
-__device__ __forceinline__ unsigned long long workgroup_index() {
-  return (unsigned long long)blockIdx.x + kGridRow * (unsigned long long)blockIdx.y;
-}
-inline dim3 sample_grid(unsigned long long wgs) {
-  return dim3((unsigned)std::min(wgs, kGridRow), (unsigned)((wgs + kGridRow - 1) / kGridRow));
-}
-
-// One lane per point, 64 consecutive points per one-wave workgroup.
-template <int O>
-__global__ void __launch_bounds__(64) k_sample_points(RenderArgs A, SampleArgs S) {
-  __shared__ SampleLds<(O & OPT_WEDGE) == 0> L;
-  const unsigned long long w = workgroup_index();
-  if (w * 64ull >= S.n) return;  // wave-uniform (the last grid row's tail)
-  const unsigned long long i = w * 64ull + threadIdx.x;
-  const bool live = i < S.n;
-  float x = 0.f, y = 0.f, z = 0.f;
-  if (live) {
-    x = S.xyz[3 * i];
-    y = S.xyz[3 * i + 1];
-    z = S.xyz[3 * i + 2];
-  }
-  float v = 0.f;
-  const bool hit = wave_locate<O>(A, S, live, x, y, z, v, L);
-  if (live) put(S, i, hit, v);
-}
-
-// The lat x lon x level grid, its points made from the three tables exactly as
-// to_cartesian_trig (irt_build.h) makes them; no xyz array exists.  A wave takes an 8 x 8
-// lat x lon patch of one level (lane = 8 * dlat + dlon), the shape of the raygen's packet:
-// neighbouring lanes share header lines, fat entries and height/value blocks.  S.n = patches;
-// patch w = (level, patch row, patch column).
-template <int O>
-__global__ void __launch_bounds__(64) k_sample_latlon(RenderArgs A, SampleArgs S) {
-  __shared__ SampleLds<(O & OPT_WEDGE) == 0> L;
-  const unsigned long long w = workgroup_index();
-  if (w >= S.n) return;  // wave-uniform
-  const unsigned long long perLevel = (unsigned long long)S.patchesLat * S.patchesLon;
-  const unsigned long long k = w / perLevel;  // < numLevels: w < S.n = numLevels * perLevel
-  const unsigned long long q = w - k * perLevel;
-  const unsigned long long j = (q / S.patchesLon) * 8ull + (threadIdx.x >> 3);
-  const unsigned long long i = (q % S.patchesLon) * 8ull + (threadIdx.x & 7u);
-  // live lanes index the tables inside their sizes: j < numLat, i < numLon
-  const bool live = j < (unsigned long long)S.numLat && i < (unsigned long long)S.numLon;
-  float x = 0.f, y = 0.f, z = 0.f;
-  if (live) {
-    const float r = S.radius[k];
-    const float t[4] = {S.latCS[2 * j], S.latCS[2 * j + 1], S.lonCS[2 * i], S.lonCS[2 * i + 1]};
-    to_cartesian_trig(r, t, x, y, z);
-  }
-  float v = 0.f;
-  const bool hit = wave_locate<O>(A, S, live, x, y, z, v, L);
-  if (live) put(S, (k * (unsigned long long)S.numLat + j) * (unsigned long long)S.numLon + i, hit, v);
-}
-
-// the cell sampler's Tracer, as k_debug_locate_wave instantiates it: from headers (with the
-// quad-bound miss test), or from the slot table where the context's frames start there
-constexpr int kCellVariant = kDefaultVariant & ~OPT_MONO;
-
-template <int O>
-void launch_points(const RenderArgs &A, const SampleArgs &S, hipStream_t s) {
-  hipLaunchKernelGGL(k_sample_points<O>, sample_grid((S.n + 63ull) / 64ull), dim3(64), 0, s, A, S);
-}
-template <int O>
-void launch_latlon(const RenderArgs &A, const SampleArgs &S, hipStream_t s) {
-  hipLaunchKernelGGL(k_sample_latlon<O>, sample_grid(S.n), dim3(64), 0, s, A, S);
-}
 
 // The scene side of a sampling launch's arguments (what debug_locate* fill for the hooks)
 void scene_args(const irt_context *c, int mode, RenderArgs &A) {
@@ -243,6 +97,71 @@ int sample_end(irt_context *c, hipStream_t s) {
   IRT_HIP(hipEventRecord(c->evSample, s));
   c->samplePending = true;
   return IRT_OK;
+}
+
+namespace {
+
+// One located point's outputs: streaming stores (nobody re-reads them in this kernel), as the
+// raygen's last frame stores its pixels.
+__device__ __forceinline__ void put(const SampleArgs &S, unsigned long long i, bool hit, float v) {
+  __builtin_nontemporal_store(hit ? v : S.missValue, &S.value[i]);
+  if (S.found) __builtin_nontemporal_store((uint8_t)(hit ? 1 : 0), &S.found[i]);
+}
+
+// One lane per point, 64 consecutive points per one-wave workgroup.
+template <int O>
+__global__ void __launch_bounds__(64) k_sample_points(RenderArgs A, SampleArgs S) {
+  __shared__ SampleLds<(O & OPT_WEDGE) == 0> L;
+  const unsigned long long w = workgroup_index();
+  if (w * 64ull >= S.n) return;  // wave-uniform (the last grid row's tail)
+  const unsigned long long i = w * 64ull + threadIdx.x;
+  const bool live = i < S.n;
+  float x = 0.f, y = 0.f, z = 0.f;
+  if (live) {
+    x = S.xyz[3 * i];
+    y = S.xyz[3 * i + 1];
+    z = S.xyz[3 * i + 2];
+  }
+  float v = 0.f;
+  const bool hit = wave_locate<O>(A, S.rLo, S.rHi, live, x, y, z, v, L);
+  if (live) put(S, i, hit, v);
+}
+
+// The lat x lon x level grid, its points made from the three tables exactly as
+// to_cartesian_trig (irt_build.h) makes them; no xyz array exists.  A wave takes an 8 x 8
+// lat x lon patch of one level (lane = 8 * dlat + dlon), the shape of the raygen's packet:
+// neighbouring lanes share header lines, fat entries and height/value blocks.  S.n = patches;
+// patch w = (level, patch row, patch column).
+template <int O>
+__global__ void __launch_bounds__(64) k_sample_latlon(RenderArgs A, SampleArgs S) {
+  __shared__ SampleLds<(O & OPT_WEDGE) == 0> L;
+  const unsigned long long w = workgroup_index();
+  if (w >= S.n) return;  // wave-uniform
+  const unsigned long long perLevel = (unsigned long long)S.patchesLat * S.patchesLon;
+  const unsigned long long k = w / perLevel;  // < numLevels: w < S.n = numLevels * perLevel
+  const unsigned long long q = w - k * perLevel;
+  const unsigned long long j = (q / S.patchesLon) * 8ull + (threadIdx.x >> 3);
+  const unsigned long long i = (q % S.patchesLon) * 8ull + (threadIdx.x & 7u);
+  // live lanes index the tables inside their sizes: j < numLat, i < numLon
+  const bool live = j < (unsigned long long)S.numLat && i < (unsigned long long)S.numLon;
+  float x = 0.f, y = 0.f, z = 0.f;
+  if (live) {
+    const float r = S.radius[k];
+    const float t[4] = {S.latCS[2 * j], S.latCS[2 * j + 1], S.lonCS[2 * i], S.lonCS[2 * i + 1]};
+    to_cartesian_trig(r, t, x, y, z);
+  }
+  float v = 0.f;
+  const bool hit = wave_locate<O>(A, S.rLo, S.rHi, live, x, y, z, v, L);
+  if (live) put(S, (k * (unsigned long long)S.numLat + j) * (unsigned long long)S.numLon + i, hit, v);
+}
+
+template <int O>
+void launch_points(const RenderArgs &A, const SampleArgs &S, hipStream_t s) {
+  hipLaunchKernelGGL(k_sample_points<O>, sample_grid((S.n + 63ull) / 64ull), dim3(64), 0, s, A, S);
+}
+template <int O>
+void launch_latlon(const RenderArgs &A, const SampleArgs &S, hipStream_t s) {
+  hipLaunchKernelGGL(k_sample_latlon<O>, sample_grid(S.n), dim3(64), 0, s, A, S);
 }
 
 void launch_sample(const irt_context *c, int mode, const RenderArgs &A, const SampleArgs &S, bool latlon,

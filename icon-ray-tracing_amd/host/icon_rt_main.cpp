@@ -17,6 +17,11 @@
 //                                                64x64 tiles dealt over them, RCCL gather
 //                                                to device 0; include/icon_rt_hip_multi.h)
 //           [--dump-fb file]                    (the final RGBA8 framebuffer, raw W*H u32)
+//           [--levels r0,r1,...]                (the field on the spheres of these radii, metres
+//                                                from the centre, in place of the volume:
+//                                                irt_render_levels; one device)
+//           [--levels-back]                     (... with the far sides of spheres the camera
+//                                                is outside of, IRT_LEVELS_BACK)
 
 #include <math.h>
 #include <stdio.h>
@@ -51,6 +56,8 @@ struct AppState {  // hostCode.cu:65-92 (the parts this backend uses)
   int mode = IRT_MODE_USER_GEOM;     // g_appState.mode: the sampler (Params.h:29-31)
   int gpus = 0;                      // > 0: the multi-GPU split over devices 0..gpus-1
   std::string dumpFb;
+  std::vector<float> levels;         // --levels: irt_render_levels in place of irt_render
+  bool levelsBack = false;
 } g;
 
 bool endsWith(const std::string &s, const std::string &suffix) {
@@ -89,6 +96,15 @@ void parseCommandLine(int argc, char *argv[]) {  // hostCode.cu:106-129
       g.gpus = atoi(argv[++i]);
     else if (arg == "--dump-fb" && i + 1 < argc)
       g.dumpFb = argv[++i];
+    else if (arg == "--levels" && i + 1 < argc) {
+      const std::string list = argv[++i];
+      for (size_t a = 0; a < list.size();) {
+        const size_t b = std::min(list.find(',', a), list.size());
+        g.levels.push_back(strtof(list.substr(a, b - a).c_str(), nullptr));
+        a = b + 1;
+      }
+    } else if (arg == "--levels-back")
+      g.levelsBack = true;
   }
 }
 
@@ -110,6 +126,10 @@ int main(int argc, char *argv[]) {
     return -1;
   }
   parseCommandLine(argc, argv);
+  if (!g.levels.empty() && (g.gpus > 0 || g.benchFrames > 0)) {
+    fprintf(stderr, "icon_rt: --levels renders on one device and has no --bench form\n");
+    return -1;
+  }
 
   // load (hostCode.cu:717-734) or synthesise
   std::vector<irt_icon_cell> cells;
@@ -211,6 +231,13 @@ int main(int argc, char *argv[]) {
   pl.setRayGen([&] {
     if (multi) {
       if (irt_multi_render(multi, &lp, fb.width, fb.height, 1, fb.fbPointer, nullptr)) dieMulti("irt_multi_render");
+      return;
+    }
+    if (!g.levels.empty()) {  // the level surfaces in place of the volume; the frame loop is the same
+      if (irt_render_levels(ctx, &lp, fb.width, fb.height, g.levels.data(), (int)g.levels.size(),
+                            g.levelsBack ? IRT_LEVELS_BACK : 0, fb.fbPointer, fb.accumBuffer, nullptr, nullptr, 0.f,
+                            nullptr))
+        die("irt_render_levels");
       return;
     }
     if (irt_render(ctx, &lp, fb.width, fb.height, fb.fbPointer, fb.accumBuffer, nullptr))

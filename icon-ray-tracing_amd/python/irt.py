@@ -32,6 +32,8 @@ ACCEL_GRID = 1         # GRID_ACCEL_MODE (Params.h:34): dda3 over the 256^3 grid
 MODE_USER_GEOM = 0     # Volume::mode (Params.h:29-31): sample() on the cells (default)
 MODE_TRIANGLES = 1     # closest bottom triangle toward the centre (deviceCode.cu:61-76)
 MODE_CUBQL = 2         # wedges + intersectWedgeEXT (deviceCode.cu:90-115)
+MAX_LEVELS = 16        # IRT_MAX_LEVELS: the most radii of one render_levels call
+LEVELS_BACK = 1        # IRT_LEVELS_BACK: also the far-side hits of spheres the camera is outside of
 # The raygen's render variants (irt_kernels.h OPT_* bits), all bit-identical: the product
 # library compiles 73405728 (the default: one-wave workgroups since round 4, 5 waves/SIMD; since
 # round 5 with the miss mode, the LDS-DMA prologue tables and the DPP prefix, and 73667872 its
@@ -152,6 +154,8 @@ def lib() -> C.CDLL:
             "irt_sample_points": [P, I, P, S, P, P, F, P],
             "irt_sample_latlon": [P, I, P, I, P, I, P, I, P, P, F, P],
             "irt_latlon_points": [P, I, P, I, P, I, P],
+            "irt_render_levels": [P, C.POINTER(LaunchParams), I, I, P, I, I, P, P, P, P, F, P],
+            "irt_levels_order": [P, I, P, P],
             "irt_debug_sample_admits": [F, F, F],
             "irt_clear_frame": [P, P, P, S, P],
             "irt_render": [P, C.POINTER(LaunchParams), I, I, P, P, P],
@@ -228,6 +232,27 @@ def _check(rc: int, what: str):
 
 def _ptr(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
+
+
+def levels_radii(radii) -> np.ndarray:
+    """render_levels' radii as the library takes them: 1 to MAX_LEVELS float32, each finite and
+    positive (checked here as irt_render_levels checks them, so that a bad list names itself)."""
+    r = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+    if not 1 <= r.size <= MAX_LEVELS:
+        raise IrtError(f"render_levels: {r.size} levels are outside [1, {MAX_LEVELS}]", E_INVALID)
+    bad = np.flatnonzero(~(np.isfinite(r) & (r > 0)))
+    if bad.size:
+        raise IrtError(f"render_levels: radius[{bad[0]}] = {r[bad[0]]} is not finite and positive", E_INVALID)
+    return r
+
+
+def levels_order(radii):
+    """irt_levels_order: (sorted, index) -- the radii in render_levels' near order (descending,
+    ties by ascending index) and each one's index into `radii`."""
+    r = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+    out, idx = np.zeros(r.size, np.float32), np.zeros(r.size, np.int32)
+    _check(lib().irt_levels_order(_ptr(r), r.size, _ptr(out), _ptr(idx)), "irt_levels_order")
+    return out, idx
 
 
 def vec3(v) -> Vec3:
@@ -900,6 +925,20 @@ class Context:
                                        C.c_void_p(found_ptr), float(miss), C.c_void_p(stream)),
                "irt_sample_latlon")
         return radius.size, lat.size, lon.size
+
+    def render_levels(self, lp: LaunchParams, width: int, height: int, radii, fb_ptr: int, accum_ptr: int,
+                      value_ptr: int = 0, level_ptr: int = 0, back: bool = False,
+                      miss: float = float("nan"), stream: int = 0):
+        """irt_render_levels: the field on the spheres of `radii` (metres from the centre, any
+        order, at most MAX_LEVELS) seen through lp's camera and the transfer function, composited
+        front to back into fb / accum (device arrays of width * height, as render's); value_ptr
+        (float32) and level_ptr (int32; an index into radii, or -1) take the first value found per
+        pixel, 0: not written.  lp.mode chooses the sampler.  Enqueued on `stream`."""
+        radii = levels_radii(radii)
+        _check(lib().irt_render_levels(self._h, C.byref(lp), int(width), int(height), _ptr(radii), radii.size,
+                                       LEVELS_BACK if back else 0, C.c_void_p(fb_ptr), C.c_void_p(accum_ptr),
+                                       C.c_void_p(value_ptr), C.c_void_p(level_ptr), float(miss),
+                                       C.c_void_p(stream)), "irt_render_levels")
 
     def resample(self, points, mode: int = MODE_USER_GEOM, miss: float = float("nan")):
         """The field at `points` (..., 3): a float32 torch tensor on the context's device (sampled

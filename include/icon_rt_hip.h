@@ -240,6 +240,61 @@ int irt_sample_latlon(irt_context *ctx, int mode, const float *lat, int numLat, 
 int irt_latlon_points(const float *lat, int numLat, const float *lon, int numLon,
                       const float *radius, int numLevels, float *xyz);
 
+/* ---------------------------------------------------------------- level surfaces
+ * The field on spheres of given radii ("the variable at 5 km"), seen from the camera through the
+ * transfer function: per pixel the raygen's own ray, its hits with the spheres, the field's value
+ * at each hit through the point location of irt_sample_points, classified and composited front to
+ * back.  Deterministic apart from the anti-aliasing jitter: one frame is the picture.  No
+ * counterpart in the reference.
+ *  - radius: HOST array of numLevels radii in metres from the Earth's centre, in any order,
+ *    copied before the call returns.  d_fb / d_accum: device arrays of width*height as for
+ *    irt_render; d_value / d_level: device arrays of width*height, either may be NULL.  Of lp the
+ *    call uses the camera, accumID, ambientColor, ambientRadiance and mode (the sampler, as in
+ *    irt_sample_points); it ignores raygen, accelMode and unitDistance.
+ *  - The ray of pixel (x, y) is the raygen's (generateRay, deviceCode.cu:36-49, with Random
+ *    rnd(accumID*W*H + x, y), 288-291), tmin = 0: a level frame lines up with an irt_render frame
+ *    of the same lp pixel for pixel.
+ *  - Hit slots.  near[] = the level indices by descending radius, ties by ascending index; far[] =
+ *    near[] reversed.  Slot h < numLevels is the near hit tn of intersectSphere(ray,
+ *    radius[near[h]]) (ShellAccel.h:34-53), live when the sphere is hit and tn > 0.  Slot
+ *    numLevels + h is the far hit tf of radius[far[h]], live when the sphere is hit, tf > 0 and
+ *    either IRT_LEVELS_BACK is set or that sphere's near slot is not live (the camera is inside
+ *    it).  Slot order is the compositing order: front to back for any camera, no sort by t.
+ *  - A live slot's point P = org + dir * t (each component o + d * t in float) is sampled exactly
+ *    as a point of irt_sample_points.  A found value v gives s = postClassify(v)
+ *    (deviceCode.cu:127-135) with the context's transfer function, a = clamp(s.w, 0, 1), c =
+ *    (s.rgb * ambientColor) * ambientRadiance, and then, in float, w = (1 - A) * a; C += w * c
+ *    (per component); A += w; C and A start at 0.
+ *  - Every pixel of the frame is written (no box test: unlike irt_render no pixel is left
+ *    untouched): (C, A) is lerped into accum with 1/(accumID+1) and fb =
+ *    make_rgba(linear_to_srgb(accum)) (deviceCode.cu:333-340); a ray that finds nothing lerps
+ *    (0, 0, 0, 0).
+ *  - d_value[p] = the value found at the first slot, in slot order, that found one, or
+ *    missValue; d_level[p] = that slot's index into the caller's radius, or -1.
+ *  - Non-finite values are outside the contract, as they are for frames: they classify as the
+ *    device's post_classify happens to.
+ *  - Ordering: a sampling call, not a launch of the ring.  It counts for everything that waits
+ *    for every launch already issued (irt_update_values*, irt_set_transfunc, irt_destroy), runs
+ *    after earlier sampling calls whatever their streams, touches no render statistics and
+ *    neither reports nor consumes IRT_E_CHAIN.  Against irt_render* calls that use the same
+ *    d_fb / d_accum it is ordered ONLY by its stream: put both on one stream, or synchronise.
+ *  - IRT_E_INVALID, nothing written: a NULL or still-building context; a pending
+ *    irt_update_values*; no transfer function set; a bad lp->mode, or a wedge or triangle mode
+ *    without irt_build_wedge_accel; numLevels outside [1, IRT_MAX_LEVELS]; a radius that is not
+ *    finite and positive; unknown flag bits; width or height < 1, or 2^27 pixels or more; NULL
+ *    lp, radius, d_fb or d_accum.
+ * The tile forms, multi-GPU splitting and several frames per launch have no level form. */
+#define IRT_MAX_LEVELS 16
+#define IRT_LEVELS_BACK 1   /* also the far-side hits of spheres the camera is outside of */
+int irt_render_levels(irt_context *ctx, const irt_launch_params *lp, int width, int height,
+                      const float *radius, int numLevels, int flags,
+                      uint32_t *d_fb, irt_vec4f *d_accum,
+                      float *d_value, int32_t *d_level, float missValue, void *stream);
+/* Host helper, no GPU: the near[] order irt_render_levels gives numLevels radii -- sorted[h] =
+ * radius[index[h]], descending, ties by ascending index.  IRT_E_INVALID for numLevels outside
+ * [1, IRT_MAX_LEVELS], a radius that is not finite and positive, or a NULL pointer. */
+int irt_levels_order(const float *radius, int numLevels, float *sorted, int32_t *index);
+
 /* == clearFramebuffer (common/pipeline.cu:171-199): fb = make_rgba(0), accum = 0. */
 int irt_clear_frame(irt_context *ctx, uint32_t *d_fb, irt_vec4f *d_accum, size_t numPixels,
                     void *stream);
