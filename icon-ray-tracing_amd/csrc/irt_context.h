@@ -142,7 +142,9 @@ struct irt_context {
   irt_render_stats total{};
   long long totalLaunches = 0;
   size_t bytes = 0;
-  int variant = irt::kDefaultVariant;  // render-kernel variant (irt_kernels.h OPT_* bits)
+  // the render-kernel variant (forms->variant: irt_kernels.h OPT_* bits) as its row of the launcher's
+  // table: never null, always a compiled variant
+  const irt::VariantForms *forms = irt::forms_of(irt::kDefaultVariant);
   // Measured-cost workgroup scheduling of the one-kernel raygen: every launch records its
   // workgroups' durations (d_schedCost); now and then a launch copies them back
   // (h_schedCost, pinned, per launch slot), and once that copy has landed the host
@@ -201,6 +203,7 @@ struct irt_context {
   bool voidOnDeviceList = false; // ... as the work-item list (else as the bitmap)
   long long lastVoid = 0;        // packets the last launch rendered as void (irt_debug_void_use)
   long long lastWorkgroups = 0;  // the last launch's raygen grid (irt_debug_last_workgroups)
+  irt::RenderPlan lastPlan{};    // ... and its kernel and grid as planned (irt_debug_last_plan)
   // persistent launches (RenderArgs::queue, IRT_QUEUE=0|1): every resident wave pulls 8x8
   // packets from per-slot queue counters (kSlots x kQueueWords u32, zero between launches)
   bool queueOn = false;

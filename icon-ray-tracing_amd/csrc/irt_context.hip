@@ -131,8 +131,8 @@ int irt_create_begin(size_t numCells, int device, irt_context **out) {
   c->device = device;
   if (const char *v = getenv("IRT_RENDER_VARIANT")) {
     const int var = atoi(v);
-    if (render_variant_available(var)) {
-      c->variant = var;
+    if (const VariantForms *f = forms_of(var)) {
+      c->forms = f;
       c->variantFixed = true;
     }
   }
@@ -434,7 +434,7 @@ int irt_create_end(irt_context *c) {
   volume_acc_finish(c->vacc, c->info);
   c->n = (uint32_t)numCells;
   const bool holes = c->voids || c->bottomMin < c->bottomMax;
-  if (!c->variantFixed && c->variant == kDefaultVariant) c->variant = scene_variant(holes);
+  if (!c->variantFixed && c->forms->variant == kDefaultVariant) c->forms = &render_forms(scene_variant(holes));
   // single frames of a scene with holes: longest 64x64 tiles first, by the durations every 8th
   // launch records (the voids' limb packets run 190-240 us against a 29 us median; C3t -7 %, flat
   // scenes even: profiles/r05r_sched/)
@@ -487,7 +487,7 @@ int irt_create_end(irt_context *c) {
                        make_float3(sb.upper.x, sb.upper.y, sb.upper.z), c->d_valueRanges, c->d_rects,
                        c->stream);
   }
-  prewarm_render(c->variant, c->stream);
+  prewarm_render(*c->forms, c->stream);
   IRT_HIP(hipGetLastError());
   IRT_HIP(hipStreamSynchronize(c->stream));
   mark("shell build");

@@ -349,7 +349,7 @@ extern "C" int irt_debug_context_array(const irt_context *c, int which, void *ds
   return IRT_OK;
 }
 
-extern "C" int irt_debug_get_variant(const irt_context *c) { return c ? c->variant : -1; }
+extern "C" int irt_debug_get_variant(const irt_context *c) { return c ? c->forms->variant : -1; }
 
 extern "C" int irt_debug_variants(int *out, int capacity) { return render_variants(out, capacity); }
 
@@ -381,12 +381,64 @@ extern "C" long long irt_debug_launch_workgroups(const irt_context *c, int numTi
     set_error("irt_debug_launch_workgroups: bad argument");
     return -1;
   }
-  RenderArgs A;
-  memset(&A, 0, sizeof(A));  // the user-geometry sphere path (sampler 0, accelMode 0)
-  const int per = render_wg_per_block(A, c->variant);
-  // a single frame in measured-cost order may add its work items (at most kMaxSplit workgroups)
-  const size_t extra = c->schedOn && numFrames == 1 && per == 4 ? (size_t)kMaxSplit : 0;
+  return irt_debug_variant_workgroups(c->forms->variant, c->schedOn ? 1 : 0, numTiles, numFrames);
+}
+
+extern "C" long long irt_debug_variant_workgroups(int variant, int sched, int numTiles, int numFrames) {
+  if (numTiles < 0 || numFrames < 1) {
+    set_error("irt_debug_variant_workgroups: bad argument");
+    return -1;
+  }
+  // the user-geometry sphere path's plain grid (no other path has more workgroups)
+  const int per = 256 / render_forms(variant).plain.threads;
+  // a single frame in measured-cost order may add its work items (at most kMaxSplit workgroups);
+  // allowed for with every one-wave-workgroup variant, also those without a split form
+  const size_t extra = sched && numFrames == 1 && per == 4 ? (size_t)kMaxSplit : 0;
   return (long long)((size_t)numTiles * 16 * per * numFrames + extra);
+}
+
+namespace {
+int plan_out(const RenderPlan &P, int out[5]) {
+  out[0] = P.form.id;
+  out[1] = P.form.threads;
+  out[2] = (int)P.grid.x;
+  out[3] = (int)P.grid.y;
+  out[4] = P.accumBlocks;
+  return IRT_OK;
+}
+}  // namespace
+
+extern "C" int irt_debug_plan(int variant, int sampler, int accelMode, int flags, int numTiles, int numFrames,
+                              uint32_t numSplit, uint32_t voidLive, uint32_t voidRow, int queueWG, int out[5]) {
+  const VariantForms *F = forms_of(variant);
+  if (!F || !out || numTiles < 0 || numFrames < 1) {
+    set_error("irt_debug_plan: variant %d not compiled, or bad argument", variant);
+    return IRT_E_INVALID;
+  }
+  alignas(16) static uint32_t set[4];  // what a flag's pointer points to (plan_render reads none of them)
+  RenderArgs A;
+  memset(&A, 0, sizeof(A));
+  A.sampler = sampler;
+  A.accelMode = accelMode;
+  A.numTiles = numTiles;
+  A.numSamples = numFrames;
+  A.numSplit = numSplit;
+  A.voidLive = voidLive;
+  A.voidRow = voidRow;
+  if (flags & IRT_DEBUG_PLAN_SLOTS) A.slots = reinterpret_cast<const float4 *>(set);
+  if (flags & IRT_DEBUG_PLAN_VOID_BITS) A.voidBits = set;
+  if (flags & IRT_DEBUG_PLAN_VOID_LIST) A.voidList = set;
+  if (flags & IRT_DEBUG_PLAN_QUEUE) A.queue = set;
+  A.chain = (flags & IRT_DEBUG_PLAN_CHAIN) ? 1 : 0;
+  return plan_out(plan_render(*F, A, queueWG), out);
+}
+
+extern "C" int irt_debug_last_plan(const irt_context *c, int out[5]) {
+  if (!c || !out) {
+    set_error("irt_debug_last_plan: null argument");
+    return IRT_E_INVALID;
+  }
+  return plan_out(c->lastPlan, out);
 }
 
 extern "C" int irt_debug_sched_split(const irt_context *c, int *numSplit, int *splitLg) {
@@ -437,10 +489,11 @@ extern "C" int irt_debug_get_queue(const irt_context *c) { return c ? (c->queueO
 extern "C" int irt_debug_queue_wgs(const irt_context *c) { return c ? c->lastQueueWG : -1; }
 
 extern "C" int irt_debug_set_variant(irt_context *c, int variant) {
-  if (!c || !render_variant_available(variant)) {
+  const VariantForms *f = forms_of(variant);
+  if (!c || !f) {
     set_error("irt_debug_set_variant: variant %d not compiled", variant);
     return IRT_E_INVALID;
   }
-  c->variant = variant;
+  c->forms = f;
   return IRT_OK;
 }

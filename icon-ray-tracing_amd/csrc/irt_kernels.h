@@ -132,7 +132,7 @@ struct RenderArgs {
   // three values in all, the headers fit the last-level cache, or IRT_SLOTS=0): slotEdge = the
   // table's edges (+inf past slotBins - 1), slotBins = table bins per slot unit, slotSubs =
   // sub-cells per slot unit (1, 2 or 4).
-  // Launches with a table run the default kernels' OPT_SLOT form (kernel_for).
+  // Launches with a table run the default kernels' OPT_SLOT form (VariantForms::slot).
   const float4 *slots;
   float slotEdge[3];
   int slotBins;
@@ -196,7 +196,7 @@ enum : int {
                            // no gain at C3, C5 3 % slower (profiles/r04b/) -- the setup waits on
                            // the majorant gather, not on asinf/atan2f
   OPT_SPLIT = 8,  // measured-cost work items (RenderArgs::splitList): the launches of a single frame
-                  // that split packets run this instantiation of the default kernels (kernel_for)
+                  // that split packets run this instantiation of the default kernels (VariantForms::split)
   OPT_DPPSCAN = 32,  // groups of 2, 4, 16 and 64 lanes take the round's prefix t0 - d0 - ... - dk
                      // by DPP steps across lanes (woodcock_wave), not each lane from LDS
   OPT_DMATAB = 67108864,  // one-wave workgroups: the LCG jump and logf tables loaded into
@@ -216,9 +216,9 @@ enum : int {
   OPT_SLOT = 128,  // the wave-wide scan starts from the slot table (RenderArgs::slots, irt_common.h
                    // kSlot4): the first admitted candidate and the list's position in one gather,
                    // instead of the header, then the entry; launches on a scene with a table run
-                   // this instantiation of the default kernels (kernel_for)
+                   // this instantiation of the default kernels (VariantForms::slot)
   OPT_VOID = 16,  // the default kernels' form for chained launches that carry a void-packet bitmap
-                  // (RenderArgs::voidList; kernel_for): the workgroup's packet is read from the list at
+                  // (RenderArgs::voidList; plan_render): the workgroup's packet is read from the list at
                   // the kernel's top.  Every other launch runs the kernels without it, as before
   OPT_VLIST = 64,  // with OPT_VOID: the launch runs rows of work items (RenderArgs::voidList) instead
                    // of the plain grid with the bitmap; the flat kernel only (the terrain kernels'
@@ -227,7 +227,7 @@ enum : int {
 };
 // OPT_MONO is kept in the numbering of round 1 (the one-kernel raygen; the setup -> march ->
 // continuation pipeline it distinguished from was removed): every listed variant sets it, and
-// kernel_for masks it off.
+// make_forms (irt_render.hip) masks it off.
 // 5376 (the default until round 4): four-wave workgroups at 5 waves/SIMD, 96 VGPRs, the few spills
 // in the prologue and epilogue only; 5120: the same kernel at 4 waves/SIMD (117 VGPRs).  70656 =
 // 5120 | OPT_SERIAL: the one-lane-per-ray Woodcock loop, against the cooperative loop.  2102272 =
@@ -262,36 +262,78 @@ constexpr uint32_t kMaxSplit = 4096;
 // mode in the same round and walks on): C3t 8 chained frames -1.7 %, one per launch even
 // (profiles/r06zg/)
 constexpr int kVoidLocBit = OPT_VOIDLOC;
-// The Tracer instantiation kernel_for picks for the unstructured samplers' sphere-accel launches
-// (256-thread workgroups, full LDS, no waves-per-SIMD floor), which k_debug_locate_sampler runs too
+// The Tracer instantiation of VariantForms::wedge, the kernel of the unstructured samplers'
+// sphere-accel launches (256-thread workgroups, full LDS, no waves-per-SIMD floor), which
+// k_debug_locate_sampler runs too
 constexpr int kSamplerVariant = ((kDefaultVariant & ~OPT_MONO) & ~(0xF00 | OPT_WAVEWG | OPT_LEAN)) | OPT_WEDGE;
 inline int scene_variant(bool holes) { return holes ? kDefaultVariant | kVoidLocBit : kDefaultVariant | kNoMissBit; }
-bool render_variant_available(int variant);
+
+// The launcher (irt_render.hip, "variants / launcher").  A variant's kernels, one per launch form:
+// fn null where the variant has no such form, id the kernel's template argument (k_render<id>),
+// threads its workgroup size.
+typedef void (*RenderKernel)(RenderArgs);
+struct KernelForm {
+  RenderKernel fn;
+  int id;
+  int threads;
+};
+struct VariantForms {
+  int variant;
+  // the user-geometry sphere path: the plain grid; a single frame's measured-cost work items first
+  // (RenderArgs::splitList); the scan from the slot table (RenderArgs::slots), and both; chained
+  // frames with the void-packet bitmap (RenderArgs::voidBits) or rows of work items
+  // (RenderArgs::voidList); the persistent launch (RenderArgs::queue)
+  KernelForm plain, split, slot, slotSplit, voidBits, voidList, queue;
+  // the grid accelerator; the unstructured samplers over the shell's spheres and over the grid
+  KernelForm grid, wedge, wedgeGrid;
+};
+const VariantForms *forms_of(int variant);  // null: not compiled
+// ... and for a variant that is not compiled the default's forms
+inline const VariantForms &render_forms(int variant) {
+  const VariantForms *f = forms_of(variant);
+  return f ? *f : *forms_of(kDefaultVariant);
+}
 int render_variants(int *out, int cap);  // the compiled variants (count; the first cap into out)
-// workgroups per 256-pixel block the launch of `variant` uses for these arguments (4 only for
-// the one-wave-workgroup A/B variants on the user-geometry sphere path)
-int render_wg_per_block(const RenderArgs &A, int variant);
-// whether `variant` can run as a persistent launch (RenderArgs::queue) with these arguments:
-// the cooperative user-geometry sphere-accel kernels with 256-thread workgroups
-bool render_queue_ok(const RenderArgs &A, int variant);
-bool render_queue_compiled();  // the A/B library (make VARIANTS=all) only
-// whether a single frame of `variant` can run measured-cost work items (RenderArgs::splitList):
-// the default kernels with one-wave workgroups
-bool render_split_ok(const RenderArgs &A, int variant);
-// whether a chained launch of `variant` with these arguments can merge its void packets
-// (RenderArgs::voidList): the default kernels with one-wave workgroups, without the slot table
-bool render_void_ok(const RenderArgs &A, int variant);
-// ... and whether it then runs the work-item list (else the bitmap on the plain grid)
-bool render_void_list_ok(int variant);
-// workgroups a persistent launch of `variant` runs on a device with numCU compute units:
-// every slot the kernel's occupancy allows (resident at once), at most `numBlocks`
-int render_queue_wgs(const RenderArgs &A, int variant, int numCU, int numBlocks);
-// numBlocks: the frame's 256-pixel blocks (grid launch), or the workgroups of a persistent
-// launch (A.queue, render_queue_wgs)
-void launch_render(const RenderArgs &A, int numBlocks, hipStream_t s, int variant);
-// one empty launch of the variant's raygen kernels (grid and persistent): the runtime's
-// first-launch setup happens at context creation, not in the first frame
-void prewarm_render(int variant, hipStream_t s);
+bool render_queue_compiled();  // some variant has a persistent form: the A/B library (make VARIANTS=all) only
+
+// What a launch may put into its arguments is read from the table: the forms below exist on the
+// user-geometry sphere path only (the grid accelerator and the samplers have one kernel each).
+inline bool render_sphere_path(const RenderArgs &A) {
+  return A.sampler == IRT_MODE_USER_GEOM && A.accelMode != IRT_ACCEL_GRID;
+}
+// a single frame can run measured-cost work items (RenderArgs::splitList)
+inline bool render_split_ok(const VariantForms &F, const RenderArgs &A) {
+  return render_sphere_path(A) && F.split.fn != nullptr;
+}
+// a chained launch can merge its void packets (RenderArgs::voidBits, or voidList where F.voidList
+// exists): these forms have no slot-table, work-item or persistent sibling
+inline bool render_void_ok(const VariantForms &F, const RenderArgs &A) {
+  return render_sphere_path(A) && F.voidBits.fn != nullptr && !A.slots && !A.queue && !A.numSplit && !A.schedOrder;
+}
+// the launch can be persistent (RenderArgs::queue)
+inline bool render_queue_ok(const VariantForms &F, const RenderArgs &A) {
+  return render_sphere_path(A) && F.queue.fn != nullptr;
+}
+// workgroups a persistent launch runs on a device with numCU compute units: every slot the queue
+// kernel's occupancy allows (resident at once), at most `numBlocks`
+int render_queue_wgs(const VariantForms &F, int numCU, int numBlocks);
+
+// One launch: its kernel, its grid (workgroups = grid.x * grid.y: what the per-workgroup count ring
+// is sized by) and k_accumulate's grid, the frame's 256-pixel blocks.
+struct RenderPlan {
+  KernelForm form;
+  dim3 grid;
+  size_t workgroups;
+  int accumBlocks;
+};
+// The only place that maps a launch's arguments to a kernel and a grid.  queueWG: the workgroups of
+// a persistent launch (A.queue; render_queue_wgs), unused otherwise.
+RenderPlan plan_render(const VariantForms &F, const RenderArgs &A, int queueWG);
+// launches the plan, and k_accumulate behind it for unchained progressive frames
+void launch_render(const RenderArgs &A, const RenderPlan &plan, hipStream_t s);
+// one empty launch of each of the variant's sphere-path kernels: the runtime's first-launch setup
+// happens at context creation, not in the first frame
+void prewarm_render(const VariantForms &F, hipStream_t s);
 void launch_debug_locate(const RenderArgs &A, const float *xyz, int n, int *found, float *value,
                          hipStream_t s, bool wave);
 // the unstructured samplers' point location (A.sampler: IRT_MODE_CUBQL or IRT_MODE_TRIANGLES)

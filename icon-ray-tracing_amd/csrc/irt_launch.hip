@@ -308,7 +308,8 @@ struct Launch {
   bool queued;     // a persistent launch ...
   int queueWG;     // ... of this many workgroups
   bool copyCosts;  // its workgroups' durations go to h_schedCost
-  size_t numWG;
+  RenderPlan plan;  // its kernel and grid (plan_render), once A says which form it takes
+  size_t numWG;     // plan.workgroups: the count ring's share, irt_debug_last_workgroups
 };
 
 // This launch runs the whole kernel: none of the measurement-only early exits (IRT_PROBE_EXIT
@@ -318,10 +319,10 @@ bool whole_kernel(const irt_context *c) { return c->probeExit == 0 || c->probeEx
 // Frames of one launch can be chained: the cooperative kernels (not the one-lane-per-ray A/B
 // variant), grid launches (`queue`: a persistent one), no measurement-only early exit
 bool chain_capable(const irt_context *c, bool queue) {
-  return c->chainOn && !queue && whole_kernel(c) && (c->variant & OPT_SERIAL) == 0;
+  return c->chainOn && !queue && whole_kernel(c) && (c->forms->variant & OPT_SERIAL) == 0;
 }
 
-bool stats_variant(const irt_context *c) { return (c->variant & (OPT_STATS | OPT_TIMING)) != 0; }  // statistics, timing
+bool stats_variant(const irt_context *c) { return (c->forms->variant & (OPT_STATS | OPT_TIMING)) != 0; }  // statistics, timing
 
 int validate(const irt_context *c, const irt_launch_params *lp, const RenderRequest &r, const uint32_t *fb,
              const irt_vec4f *accum) {
@@ -460,29 +461,28 @@ int claim_slot(irt_context *c, Launch &L) {
 // (every wave must reach the queue's done count)
 void decide_queue(irt_context *c, int numFrames, Launch &L) {
   RenderArgs &A = L.A;
-  L.queued = c->queueOn && L.numTiles > 0 && whole_kernel(c) && render_queue_ok(A, c->variant);
+  L.queued = c->queueOn && L.numTiles > 0 && whole_kernel(c) && render_queue_ok(*c->forms, A);
   L.queueWG = 0;
   if (!L.queued) return;
   A.queue = c->d_queue + (size_t)kQueueWords * L.slot;
   A.numPackets = (uint32_t)L.numTiles * 64u * (uint32_t)numFrames;
   L.queueWG = c->queuePerCU > 0 ? std::min(c->queuePerCU * c->numCU, L.numTiles * 16 * numFrames)
-                                : render_queue_wgs(A, c->variant, c->numCU, L.numTiles * 16 * numFrames);
+                                : render_queue_wgs(*c->forms, c->numCU, L.numTiles * 16 * numFrames);
   c->lastQueueWG = L.queueWG;
 }
 
-// measured-cost scheduling: single-frame launches of the one-kernel raygen only (before the
-// workgroup count: the split packets' parts are extra workgroups)
+// measured-cost scheduling: single-frame launches of the one-kernel raygen only
 int decide_sched(irt_context *c, const irt_launch_params *lp, const RenderRequest &r, Launch &L) {
   RenderArgs &A = L.A;
   const int numBlocks = L.numTiles * 16;
   L.copyCosts = false;
   if (!(c->schedOn && r.numFrames == 1 && numBlocks > 0 && !A.tileList && !L.queued)) return IRT_OK;
   int rc = sched_prepare(c, numBlocks, r.W, r.H, r.packed, r.tileBegin, r.tileStride, L.numTiles, lp,
-                         render_split_ok(A, c->variant), L.s);
+                         render_split_ok(*c->forms, A), L.s);
   if (rc) return rc;
   const uint32_t *ob = c->d_schedOrder + (size_t)c->schedBuf * sched_stride(c->schedCap);
   A.schedOrder = c->schedOrderValid ? ob : nullptr;
-  if (c->schedOrderValid && c->schedSplit[c->schedBuf] && render_split_ok(A, c->variant) && whole_kernel(c)) {
+  if (c->schedOrderValid && c->schedSplit[c->schedBuf] && render_split_ok(*c->forms, A) && whole_kernel(c)) {
     A.splitList = ob + c->schedCap;
     A.splitMask = ob + c->schedCap + kMaxSplit;
     A.numSplit = c->schedSplit[c->schedBuf];
@@ -500,10 +500,8 @@ int decide_sched(irt_context *c, const irt_launch_params *lp, const RenderReques
   return IRT_OK;
 }
 
-// Whether the frames are chained, and the workgroups of this launch: 16 per 64x64 tile, x4 for
-// the one-wave-workgroup variants (OPT_WAVEWG), per frame, + the split packets' parts; a
-// persistent launch's resident ones
-void count_workgroups(const irt_context *c, const RenderRequest &r, Launch &L) {
+// Whether the frames are chained
+void decide_chain(const irt_context *c, const RenderRequest &r, Launch &L) {
   RenderArgs &A = L.A;
   // The hand-off's buffer resources address accum with 32-bit byte offsets: frames of 2^27
   // pixels or more (11,585^2) go through the sample buffer instead
@@ -511,9 +509,6 @@ void count_workgroups(const irt_context *c, const RenderRequest &r, Launch &L) {
   // (decided from whether this launch is in fact queued: see render_sequence)
   A.chain = r.numFrames > 1 && chain_capable(c, L.queued) && outPixels * 16u <= 0x7FFFFFFFull ? 1 : 0;
   A.numSamples = r.numFrames;
-  L.numWG = L.queued ? (size_t)L.queueWG
-                     : (size_t)L.numTiles * 16 * (size_t)render_wg_per_block(A, c->variant) * (size_t)r.numFrames +
-                           (size_t)A.numSplit;
 }
 
 // Where the launch counts its events: per workgroup in pinned memory (A.wgCounts), in the
@@ -590,10 +585,9 @@ int setup_chain(irt_context *c, int numFrames, Launch &L) {
 
 // Void packets (RenderArgs::voidList, host/irt_void.cpp): chained progressive frames of one camera
 // render the packets that can only ever give the zero colour once per launch, and dispatch no other
-// workgroup for them: the launch runs rows of work items (VoidLists) instead of the plain grid, so
-// its workgroup count (L.numWG: the count ring, irt_debug_last_workgroups) is set here, before the
-// counters are chosen.  Only launches that can use the list compute it -- several chained frames of
-// one camera through the default kernels (render_void_ok), the raygen over the shell's spheres, at
+// workgroup for them: the launch runs rows of work items (VoidLists) instead of the plain grid
+// (plan_render, from the arguments set here).  Only launches that can use the list compute it --
+// several chained frames of one camera through the default kernels (render_void_ok), the raygen over the shell's spheres, at
 // most 65,535 of them (a grid's rows: a void wave's counts, 64 x numFrames, then fit its 32-bit
 // words); not with the chain test hook set
 // (its withheld frame must stall every packet), a measurement-only exit or the statistics and
@@ -613,7 +607,7 @@ int prepare_void(irt_context *c, const irt_launch_params *lp, const RenderReques
   if (!(A.chain && !r.seq && r.numFrames > 1 && r.numFrames <= 65535 && L.numTiles > 0 &&
         c->chainWithhold < 0 && c->probeExit == 0 && !stats_variant(c) &&
         lp->raygen == IRT_RAYGEN_WITH_ACCEL && lp->accelMode == IRT_ACCEL_SPHERE &&
-        render_void_ok(A, c->variant)))
+        render_void_ok(*c->forms, A)))
     return IRT_OK;
   c->voidCache.lookup(void_request(*lp, c->info, r.W, r.H, r.tileBegin, r.tileStride, L.numTiles, r.tileList), true);
   const VoidLists &vl = c->voidCache.lists;
@@ -622,7 +616,7 @@ int prepare_void(irt_context *c, const irt_launch_params *lp, const RenderReques
   // frame the residues' padding can outweigh the merged packets: 64x64 FRAMING, 64 + 8 against 64) --
   // so no launch has more workgroups than irt_debug_launch_workgroups says.  Every other launch: the
   // bitmap on the plain grid (the terrain kernels always).
-  const bool list = render_void_list_ok(c->variant) &&
+  const bool list = c->forms->voidList.fn != nullptr &&
                     (size_t)vl.live + void_row(vl.count, r.numFrames) < (size_t)L.numTiles * 64;
   const size_t words = list ? vl.items.size() : void_words(L.numTiles);
   if (words > c->voidCap) {
@@ -646,7 +640,6 @@ int prepare_void(irt_context *c, const irt_launch_params *lp, const RenderReques
     A.voidLive = vl.live;
     A.voidRow = void_row(vl.count, r.numFrames);
     A.voidCount = vl.count;
-    L.numWG = ((size_t)A.voidLive + A.voidRow) * (size_t)r.numFrames;  // launch_variant's grid
   } else {
     A.voidBits = c->d_voidList;
   }
@@ -706,6 +699,7 @@ int launch_and_commit(irt_context *c, Launch &L) {
   c->schedLastApplied = A.schedOrder != nullptr;
   c->lastNumSplit = A.numSplit;
   c->lastWorkgroups = L.numTiles > 0 ? (long long)L.numWG : 0;
+  c->lastPlan = L.plan;
   c->schedApplied += c->schedLastApplied ? 1 : 0;
   // the 16-counter block (device atomics) is only needed by the statistics variant and the
   // IRT_COUNTERS=atomic mode; it must start zeroed
@@ -715,9 +709,7 @@ int launch_and_commit(irt_context *c, Launch &L) {
   if (block && !c->lastBlock) IRT_HIP(hipMemsetAsync(A.counters, 0, 16 * sizeof(unsigned long long), s));
   r.timed = c->launches % c->timingEvery == 0;
   if (r.timed) IRT_HIP(hipEventRecord(r.ev0, s));
-  if (L.numTiles > 0) {
-    launch_render(A, L.queued ? L.queueWG : L.numTiles * 16, s, c->variant);
-  }
+  if (L.numTiles > 0) launch_render(A, L.plan, s);
   IRT_HIP(hipGetLastError());
   if (r.timed) IRT_HIP(hipEventRecord(r.ev1, s));
   if (block) {
@@ -760,8 +752,12 @@ int render_impl(irt_context *c, const irt_launch_params *lp, const RenderRequest
   if ((rc = claim_slot(c, L))) return rc;
   decide_queue(c, r.numFrames, L);
   if ((rc = decide_sched(c, lp, r, L))) return rc;
-  count_workgroups(c, r, L);
-  if ((rc = prepare_void(c, lp, r, L)) || (rc = choose_counters(c, L)) || (rc = setup_chain(c, r.numFrames, L)) ||
+  decide_chain(c, r, L);
+  if ((rc = prepare_void(c, lp, r, L))) return rc;
+  // the launch's form is settled: its kernel and grid, which the count ring is sized by
+  L.plan = plan_render(*c->forms, L.A, L.queueWG);
+  L.numWG = L.plan.workgroups;
+  if ((rc = choose_counters(c, L)) || (rc = setup_chain(c, r.numFrames, L)) ||
       (rc = stage_sequence(c, r, L)) ||
       (rc = ensure_samples(c, r.numFrames, L)))
     return rc;
@@ -793,7 +789,7 @@ int render_sequence(irt_context *c, const irt_launch_params *lps, int numFrames,
       set_error("irt_render_sequence: frame %d differs from frame 0 in more than the camera and accumID", k);
       return IRT_E_INVALID;
     }
-  // Not the decision render_impl makes (count_workgroups): here persistent launches being on
+  // Not the decision render_impl makes (decide_chain): here persistent launches being on
   // (queueOn) rules chaining out, there only a launch that is in fact queued does, and there the
   // 2^27-pixel limit applies too.  With queueOn and a launch the queue cannot take, the views
   // therefore go one per launch although one launch could chain them; past the pixel limit the

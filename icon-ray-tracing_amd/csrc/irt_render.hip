@@ -23,6 +23,8 @@
 // write) and this file -- the persistent launch's packet queue, the kernels (k_render,
 // k_accumulate, the three k_debug_locate*) and the variant list with its launchers.
 
+#include <initializer_list>
+
 #include "irt_raygen.h"
 
 namespace irt {
@@ -100,7 +102,7 @@ __global__ void __launch_bounds__((OPT & OPT_WAVEWG) ? 64 : 256,
   }
   if (A.probeExit == 1) return;  // measurement only
   // Void packets (OPT_VOID: the kernels of launches with A.voidList -- chained progressive frames of
-  // one camera; irt_launch.hip prepare_void, kernel_for): the workgroup's packet from the launch's
+  // one camera; irt_launch.hip prepare_void, plan_render): the workgroup's packet from the launch's
   // work-item list, by the scalar unit, before anything else is in flight -- the prologue's LDS-DMA
   // included.  Such a launch has no block order and no split items.  Row (blockIdx.y = frame) y is
   // voidLive live items, the same in every row, then voidRow void items (RenderArgs::voidList).
@@ -503,7 +505,7 @@ void launch_debug_locate(const RenderArgs &A, const float *xyz, int n, int *foun
 
 // The unstructured samplers' point location (Tracer::locate_wedge for IRT_MODE_CUBQL,
 // Tracer::locate_tri for IRT_MODE_TRIANGLES, chosen by A.sampler) on given points, through the
-// Tracer instantiation kernel_for picks for their sphere-accel launches (kSamplerVariant): the
+// Tracer instantiation of their sphere-accel launches (VariantForms::wedge, kSamplerVariant): the
 // frames' own code on records and points a frame almost never samples
 // (tests/test_gpu_samplers.py).
 __global__ void __launch_bounds__(256) k_debug_locate_sampler(RenderArgs A, const float *xyz, int n,
@@ -531,7 +533,16 @@ void launch_debug_locate_sampler(const RenderArgs &A, const float *xyz, int n, i
 // Variant numbers: irt_kernels.h OPT_* (the numbering is explained there).
 static_assert((kDefaultVariant & OPT_MONO) != 0, "variant numbering");
 
-// The product build instantiates the default (one-wave workgroups) with its two scene forms, 5376
+// A launch's kernel and grid are one value, RenderPlan, computed in one function, plan_render, from
+// the launch's arguments and its variant's row of the table below; everything else reads it: the
+// launch itself, the count ring's size, the debug hooks.  The table has one VariantForms per listed
+// variant, filled by make_forms<N>: the k_render instantiation of each form a launch of variant N
+// can take, null where N has none.  Which forms exist is decided there and nowhere else -- what
+// irt_launch.hip may put into RenderArgs (render_split_ok & co., irt_kernels.h), what
+// prewarm_render launches and what render_queue_wgs measures are reads of the table.  A new form
+// is a new member, its line in make_forms and its test in plan_render.
+//
+// The product build lists the default (one-wave workgroups) with its two scene forms, 5376
 // (four-wave workgroups) and the statistics variant (IRT_COUNTERS, profiles/wave_stats.py).  The
 // A/B variants are built only by `make VARIANTS=all` (libicon_rt_hip_all.so, loaded through
 // IRT_LIB_PATH by the profiles/ tools and by tests/test_gpu_parity.py when present), one line per
@@ -560,118 +571,115 @@ static_assert(kDefaultVariant == 73405728 && (kDefaultVariant | kNoMissBit) == 7
                   (kDefaultVariant | kVoidLocBit) == 1147147552 && kVoidLocBit == OPT_VOIDLOC,
               "the product build's variant list names the default and its scene forms (scene_variant)");
 
-int render_variants(int *out, int cap) {
-  int n = 0;
-#define IRT_LIST(N) \
-  if (n < cap && out) out[n] = N; \
-  ++n;
-  IRT_VARIANTS(IRT_LIST)
-#undef IRT_LIST
-  return n;
+// k_render<ID> as a launch form: one-wave workgroups (OPT_WAVEWG) run four per 256-pixel block
+template <int ID>
+constexpr KernelForm form() {
+  return {k_render<ID>, ID, (ID & OPT_WAVEWG) ? 64 : 256};
 }
 
-bool render_variant_available(int v) {
-#define IRT_CASE(N) if (v == N) return true;
-  IRT_VARIANTS(IRT_CASE)
-#undef IRT_CASE
-  return false;
-}
-
-int render_wg_per_block(const RenderArgs &A, int variant) {
-  const int per = (variant & OPT_WAVEWG) ? 4 : 1;
-  return render_variant_available(variant) && A.sampler == IRT_MODE_USER_GEOM && A.accelMode != IRT_ACCEL_GRID ? per : 1;
-}
-
-// variant bits without a persistent form
-constexpr int kNoQueue = OPT_WAVEWG | OPT_SERIAL | OPT_STATS | OPT_TIMING;
-// Persistent launches (OPT_QUEUE, 3-4x slower: DESIGN.md section 5) are compiled into the A/B
-// library only (make VARIANTS=all); the product library has no persistent kernel.
-bool render_split_ok(const RenderArgs &A, int variant) {
-  return (variant == kDefaultVariant || variant == (kDefaultVariant | kNoMissBit) || variant == (kDefaultVariant | OPT_VOIDLOC)) &&
-         render_wg_per_block(A, variant) == 4;
-}
-
-// (kernel_for then picks the OPT_VOID form, which has no OPT_SLOT or OPT_SPLIT sibling)
-bool render_void_list_ok(int variant) { return variant == (kDefaultVariant | kNoMissBit); }
-bool render_void_ok(const RenderArgs &A, int variant) {
-  return render_split_ok(A, variant) && !A.slots && !A.queue && !A.numSplit && !A.schedOrder;
-}
-
-bool render_queue_compiled() {
-#ifdef IRT_ALL_VARIANTS
-  return true;
-#else
-  return false;
-#endif
-}
-bool render_queue_ok(const RenderArgs &A, int variant) {
-  return render_queue_compiled() && render_variant_available(variant) && (variant & kNoQueue) == 0 &&
-         A.sampler == IRT_MODE_USER_GEOM && A.accelMode != IRT_ACCEL_GRID;
-}
-
-typedef void (*RenderKernel)(RenderArgs);
-// The kernel a launch of variant N runs for these arguments, and its workgroup size.  The
-// grid accel or the unstructured samplers: their own instantiations of the raygen (kept out
-// of the default kernel, whose registers they would cost); the wedge kernels hold a 6-vertex
-// Newton state: no waves-per-SIMD floor.  Both run the cooperative Woodcock loop with its
-// miss mode (C2: TRIANGLES 3.4x, CUBQL 2.5x faster than one lane per ray;
+// The forms of variant N.  The grid accel and the unstructured samplers: their own instantiations
+// of the raygen (kept out of the default kernel, whose registers they would cost); the wedge
+// kernels hold a 6-vertex Newton state: no waves-per-SIMD floor.  Both run the cooperative
+// Woodcock loop with its miss mode (C2: TRIANGLES 3.4x, CUBQL 2.5x faster than one lane per ray;
 // profiles/r02b_investigation/).
 template <int N>
-RenderKernel kernel_for(const RenderArgs &A, int &threads) {
+constexpr VariantForms make_forms() {
   constexpr int K = N & ~OPT_MONO;
   constexpr int D = kDefaultVariant & ~OPT_MONO;
   constexpr int DB = D & ~(0xF00 | OPT_WAVEWG | OPT_LEAN);  // 256-thread workgroups, full LDS
   constexpr int DW = DB | OPT_WEDGE | (K & OPT_SERIAL);
   static_assert(DW == (kSamplerVariant | (K & OPT_SERIAL)), "k_debug_locate_sampler runs the samplers' Tracer");
   constexpr int DG = DB | 0x400;  // the grid-accel raygen: 4 waves/SIMD as measured in round 2
-  const bool g = A.accelMode == IRT_ACCEL_GRID;
-  threads = 256;
-  if (A.sampler != IRT_MODE_USER_GEOM && g) return k_render<DW | OPT_GRID>;  // CUBQL / TRIANGLES
-  if (A.sampler != IRT_MODE_USER_GEOM) return k_render<DW>;
-  if (g) return k_render<DG | OPT_GRID | (K & OPT_SERIAL)>;
-  if ((K & OPT_WAVEWG) != 0) threads = 64;  // four one-wave workgroups per 256-pixel block
+  VariantForms f = {};
+  f.variant = N;
+  f.plain = form<K>();
+  f.wedgeGrid = form<DW | OPT_GRID>();  // CUBQL / TRIANGLES
+  f.wedge = form<DW>();
+  f.grid = form<DG | OPT_GRID | (K & OPT_SERIAL)>();
+  // Persistent launches (OPT_QUEUE, 3-4x slower: DESIGN.md section 5) are compiled into the A/B
+  // library only (make VARIANTS=all); the product library has no persistent kernel.
 #ifdef IRT_ALL_VARIANTS
-  if constexpr ((K & kNoQueue) == 0)
-    if (A.queue) return k_render<K | OPT_QUEUE>;
+  constexpr int kNoQueue = OPT_WAVEWG | OPT_SERIAL | OPT_STATS | OPT_TIMING;  // bits without a persistent form
+  if constexpr ((K & kNoQueue) == 0) f.queue = form<K | OPT_QUEUE>();
 #endif
-  // a single frame with measured-cost work items: the default kernels' split-capable form
-  // and a scene with a slot table: their OPT_SLOT form
-  if constexpr (K == (kDefaultVariant & ~OPT_MONO) || K == ((kDefaultVariant | kNoMissBit) & ~OPT_MONO) ||
-                K == ((kDefaultVariant | OPT_VOIDLOC) & ~OPT_MONO)) {
-    // chained progressive frames with a void-packet work-item list (render_void_ok: no table, no
-    // split items)
-    if constexpr (K == ((kDefaultVariant | kNoMissBit) & ~OPT_MONO))
-      if (A.voidList) return k_render<K | OPT_VOID | OPT_VLIST>;
-    if (A.voidBits) return k_render<K | OPT_VOID>;  // (the terrain kernels: the bitmap, the plain grid)
-    if (A.slots) return A.numSplit ? k_render<K | OPT_SPLIT | OPT_SLOT> : k_render<K | OPT_SLOT>;
-    if (A.numSplit) return k_render<K | OPT_SPLIT>;
+  // The default and its two scene forms: a single frame with measured-cost work items runs their
+  // split-capable form, a scene with a slot table their OPT_SLOT form, ...
+  if constexpr (K == D || K == (D | kNoMissBit) || K == (D | kVoidLocBit)) {
+    f.split = form<K | OPT_SPLIT>();
+    f.slot = form<K | OPT_SLOT>();
+    f.slotSplit = form<K | OPT_SPLIT | OPT_SLOT>();
+    // ... and chained progressive frames with void packets the OPT_VOID form, which has no OPT_SLOT
+    // or OPT_SPLIT sibling (render_void_ok): the bitmap on the plain grid, and for the flat kernel
+    // the work-item list (k_render: the terrain kernels' list form needs scratch)
+    f.voidBits = form<K | OPT_VOID>();
+    if constexpr (K == (D | kNoMissBit)) f.voidList = form<K | OPT_VOID | OPT_VLIST>();
   }
-  return k_render<K>;
+  return f;
 }
 
-template <int N>
-void launch_variant(const RenderArgs &A, int numBlocks, hipStream_t s) {
-  int threads = 256;
-  const RenderKernel k = kernel_for<N>(A, threads);
-  if (A.queue) {  // persistent: numBlocks workgroups (render_queue_wgs) pull the packets
-    hipLaunchKernelGGL(k, dim3(numBlocks), dim3(256), 0, s, A);
-    numBlocks = A.numTiles * 16;
-  } else {
-    const int split = A.numSplit ? (int)A.numSplit : 0;  // the listed work items first (kernel_for: OPT_SPLIT)
-    // a launch with a void-packet list (kernel_for: OPT_VOID): its rows of live and void items
-    const uint32_t gx = A.voidList ? A.voidLive + A.voidRow : (uint32_t)(numBlocks * (256 / threads) + split);
-    hipLaunchKernelGGL(k, dim3(gx, A.numSamples), dim3(threads), 0, s, A);
+constexpr VariantForms kForms[] = {
+#define IRT_FORMS(N) make_forms<N>(),
+    IRT_VARIANTS(IRT_FORMS)
+#undef IRT_FORMS
+};
+
+const VariantForms *forms_of(int variant) {
+  for (const VariantForms &f : kForms)
+    if (f.variant == variant) return &f;
+  return nullptr;
+}
+
+int render_variants(int *out, int cap) {
+  int n = 0;
+  for (const VariantForms &f : kForms) {
+    if (n < cap && out) out[n] = f.variant;
+    ++n;
   }
+  return n;
+}
+
+bool render_queue_compiled() {
+  for (const VariantForms &f : kForms)
+    if (f.queue.fn) return true;
+  return false;
+}
+
+// The precedence: the samplers, the grid accelerator, then the sphere path's forms -- queue, void
+// list, void bitmap, slot table, work items -- each only where the variant has it.  The grid follows
+// from the form chosen, never from the arguments alone.
+RenderPlan plan_render(const VariantForms &F, const RenderArgs &A, int queueWG) {
+  const bool g = A.accelMode == IRT_ACCEL_GRID;
+  const KernelForm *k = &F.plain;
+  if (A.sampler != IRT_MODE_USER_GEOM) k = g ? &F.wedgeGrid : &F.wedge;
+  else if (g) k = &F.grid;
+  else if (A.queue && F.queue.fn) k = &F.queue;
+  else if (A.voidList && F.voidList.fn) k = &F.voidList;
+  else if (A.voidBits && F.voidBits.fn) k = &F.voidBits;
+  else if (A.slots && F.slot.fn) k = A.numSplit ? &F.slotSplit : &F.slot;
+  else if (A.numSplit && F.split.fn) k = &F.split;
+  RenderPlan P;
+  P.form = *k;
+  P.accumBlocks = A.numTiles * 16;
+  if (k == &F.queue)  // persistent: the resident workgroups pull the packets
+    P.grid = dim3((uint32_t)queueWG, 1);
+  else if (k == &F.voidList)  // rows of live and void work items, one row per frame
+    P.grid = dim3(A.voidLive + A.voidRow, (uint32_t)A.numSamples);
+  else  // the frame's blocks, behind the listed work items (A.numSplit), per frame
+    P.grid = dim3((uint32_t)(P.accumBlocks * (256 / k->threads)) + A.numSplit, (uint32_t)A.numSamples);
+  P.workgroups = (size_t)P.grid.x * P.grid.y;
+  return P;
+}
+
+void launch_render(const RenderArgs &A, const RenderPlan &P, hipStream_t s) {
+  hipLaunchKernelGGL(P.form.fn, P.grid, dim3(P.form.threads), 0, s, A);
   // progressive batch: the lerp chain over the frames' samples (chained frames lerp in k_render)
-  if (A.numSamples > 1 && !A.chain) hipLaunchKernelGGL(k_accumulate, dim3(numBlocks), dim3(256), 0, s, A);
+  if (A.numSamples > 1 && !A.chain) hipLaunchKernelGGL(k_accumulate, dim3(P.accumBlocks), dim3(256), 0, s, A);
 }
 
-template <int N>
-int queue_wgs_variant(const RenderArgs &A, int numCU, int numBlocks) {
-  int threads = 256;
-  const RenderKernel k = kernel_for<N>(A, threads);
+int render_queue_wgs(const VariantForms &F, int numCU, int numBlocks) {
   int occ = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, threads, 0) != hipSuccess || occ < 1) {
+  if (!F.queue.fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, F.queue.fn, F.queue.threads, 0) != hipSuccess ||
+      occ < 1) {
     (void)hipGetLastError();
     occ = 1;
   }
@@ -679,76 +687,18 @@ int queue_wgs_variant(const RenderArgs &A, int numCU, int numBlocks) {
   return (int)(n < numBlocks ? n : numBlocks);
 }
 
-int render_queue_wgs(const RenderArgs &A, int variant, int numCU, int numBlocks) {
-  switch (variant) {
-#define IRT_CASE(N) \
-  case N:           \
-    return queue_wgs_variant<N>(A, numCU, numBlocks);
-    IRT_VARIANTS(IRT_CASE)
-#undef IRT_CASE
-    default:
-      return queue_wgs_variant<kDefaultVariant>(A, numCU, numBlocks);
-  }
-}
-
 // The first launch of a kernel pays the HIP runtime's lazy per-kernel setup on the host
 // (~0.6 ms between the launch's start event and the dispatch, against a ~0.1 ms frame): a
-// one-workgroup launch that returns at once (probeExit 1) at context creation takes it there.
-template <int N>
-void prewarm_variant(hipStream_t s) {
+// one-workgroup launch that returns at once (probeExit 1) at context creation takes it there,
+// for every form of the sphere path (the grid accelerator's and the samplers' kernels pay it in
+// their first frame).
+void prewarm_render(const VariantForms &F, hipStream_t s) {
   RenderArgs A = {};
   A.probeExit = 1;
   A.numSamples = 1;
-  int threads = 256;
-  const RenderKernel k = kernel_for<N>(A, threads);  // sets threads (64 for one-wave workgroups)
-  hipLaunchKernelGGL(k, dim3(1), dim3(threads), 0, s, A);
-  A.numSplit = 8;  // the split-capable form of the default kernels (never read: it returns first)
-  const RenderKernel ks = kernel_for<N>(A, threads);
-  if (ks != k) hipLaunchKernelGGL(ks, dim3(1), dim3(threads), 0, s, A);
-  A.slots = reinterpret_cast<const float4 *>(16);  // and the slot-table forms (never dereferenced)
-  const RenderKernel kts = kernel_for<N>(A, threads);
-  if (kts != ks) hipLaunchKernelGGL(kts, dim3(1), dim3(threads), 0, s, A);
-  A.numSplit = 0;
-  const RenderKernel kt = kernel_for<N>(A, threads);
-  if (kt != k) hipLaunchKernelGGL(kt, dim3(1), dim3(threads), 0, s, A);
-  A.slots = nullptr;
-  A.voidList = reinterpret_cast<const uint32_t *>(16);  // the void-packet form (never dereferenced)
-  const RenderKernel kv = kernel_for<N>(A, threads);
-  if (kv != k) hipLaunchKernelGGL(kv, dim3(1), dim3(threads), 0, s, A);
-  A.voidList = nullptr;
-  A.voidBits = reinterpret_cast<const uint32_t *>(16);  // and the bitmap form (likewise)
-  const RenderKernel kb = kernel_for<N>(A, threads);
-  if (kb != k && kb != kv) hipLaunchKernelGGL(kb, dim3(1), dim3(threads), 0, s, A);
-  A.voidBits = nullptr;
-  A.queue = reinterpret_cast<uint32_t *>(16);  // never dereferenced: the kernel returns first
-  const RenderKernel kq = kernel_for<N>(A, threads);
-  if (kq != kernel_for<N>(RenderArgs{}, threads)) hipLaunchKernelGGL(kq, dim3(1), dim3(256), 0, s, A);
-}
-
-void prewarm_render(int variant, hipStream_t s) {
-  switch (variant) {
-#define IRT_CASE(N) \
-  case N:           \
-    prewarm_variant<N>(s); \
-    return;
-    IRT_VARIANTS(IRT_CASE)
-#undef IRT_CASE
-    default:
-      prewarm_variant<kDefaultVariant>(s);
-  }
-}
-
-void launch_render(const RenderArgs &A, int numBlocks, hipStream_t s, int variant) {
-  switch (variant) {
-#define IRT_CASE(N) \
-  case N:           \
-    launch_variant<N>(A, numBlocks, s); \
-    return;
-    IRT_VARIANTS(IRT_CASE)
-#undef IRT_CASE
-    default:
-      launch_variant<kDefaultVariant>(A, numBlocks, s);
-  }
+  for (const KernelForm *k : {&F.plain, &F.split, &F.slotSplit, &F.slot, &F.voidList, &F.voidBits, &F.queue})
+    if (k->fn) hipLaunchKernelGGL(k->fn, dim3(1), dim3(k->threads), 0, s, A);
 }
 
 }  // namespace irt
+

@@ -269,7 +269,11 @@ def default_kernel_id(ctx=None) -> int:
     launches -- the default variant, its hole-free form (bit 262144) on scenes without holes
     or its located-mode void walk (bit 1073741824) on scenes with holes, with bit 128 (OPT_SLOT)
     where the launches use the slot table (irt_debug_slot_use) -- or, without a context,
-    that of the default variant."""
+    that of the default variant.
+
+    A restatement of the library's launch plan kept for the profile lookups keyed on it, not a
+    read of it: after a launch that ran the void work-item list it says | 16 where the kernel was
+    the | 16 | 64 one.  Context.last_plan() gives the kernel the last launch in fact ran."""
     L = lib()
     if ctx is not None:
         L.irt_debug_get_variant.argtypes = [C.c_void_p]
@@ -277,11 +281,38 @@ def default_kernel_id(ctx=None) -> int:
         d = int(L.irt_debug_default_variant())
         L.irt_debug_slot_use.argtypes = [C.c_void_p, C.c_void_p]
         if v in ((d & ~4096), (d | 262144) & ~4096, (d | 1073741824) & ~4096) and L.irt_debug_slot_use(ctx._h, None) == 1:
-            v |= 128  # kernel_for: the default kernels' OPT_SLOT form
+            v |= 128  # VariantForms::slot: the default kernels' OPT_SLOT form
         elif ctx.void_use() > 0:
             v |= 16  # ... their OPT_VOID form: the last launch carried a void-packet bitmap
         return v
     return int(L.irt_debug_default_variant()) & ~4096  # OPT_MONO: one kernel per frame
+
+
+PLAN_SLOTS, PLAN_VOID_BITS, PLAN_VOID_LIST, PLAN_QUEUE, PLAN_CHAIN = 1, 2, 4, 8, 16  # IRT_DEBUG_PLAN_*
+
+
+def plan(variant: int, sampler: int = 0, accel: int = 0, flags: int = 0, tiles: int = 1, frames: int = 1,
+         num_split: int = 0, void_live: int = 0, void_row: int = 0, queue_wg: int = 0) -> tuple:
+    """irt_debug_plan (no device): (kernel id, threads, grid x, grid y, k_accumulate blocks) of a
+    launch of `variant` with these arguments; flags: PLAN_* bits."""
+    L = lib()
+    L.irt_debug_plan.argtypes = [C.c_int] * 6 + [C.c_uint32] * 3 + [C.c_int, C.POINTER(C.c_int)]
+    out = (C.c_int * 5)()
+    _check(L.irt_debug_plan(variant, sampler, accel, flags, tiles, frames, num_split, void_live, void_row,
+                            queue_wg, out), "irt_debug_plan")
+    return tuple(out)
+
+
+def variant_workgroups(variant: int, sched: bool, num_tiles: int, frames: int = 1) -> int:
+    """irt_debug_variant_workgroups (no device): Context.launch_workgroups for a context of
+    `variant` with measured-cost scheduling on or off."""
+    L = lib()
+    L.irt_debug_variant_workgroups.argtypes = [C.c_int] * 4
+    L.irt_debug_variant_workgroups.restype = C.c_longlong
+    n = L.irt_debug_variant_workgroups(variant, 1 if sched else 0, num_tiles, frames)
+    if n < 0:
+        raise IrtError("irt_debug_variant_workgroups failed")
+    return n
 
 
 def synth_grid(root_n: int, bisections: int, levels: int, top_height: float = 75e3,
@@ -784,6 +815,15 @@ class Context:
         L.irt_debug_last_workgroups.argtypes = [C.c_void_p]
         L.irt_debug_last_workgroups.restype = C.c_longlong
         return L.irt_debug_last_workgroups(self._h)
+
+    def last_plan(self) -> tuple:
+        """irt_debug_last_plan: (kernel id, threads, grid x, grid y, k_accumulate blocks) of the
+        last launch, as irt.plan gives them."""
+        L = lib()
+        L.irt_debug_last_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        out = (C.c_int * 5)()
+        _check(L.irt_debug_last_plan(self._h, out), "irt_debug_last_plan")
+        return tuple(out)
 
     def launch_workgroups(self, num_tiles: int, frames: int = 1) -> int:
         """Workgroups of one launch of num_tiles tiles x frames (the wg-trace buffer needs 4

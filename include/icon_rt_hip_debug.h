@@ -176,6 +176,29 @@ int irt_debug_set_wg_trace(irt_context *ctx, uint32_t *trace);
  * words; with measured-cost scheduling a single frame adds up to 4096 workgroups for its work
  * items, which come first; rows a launch does not use stay as they were). */
 long long irt_debug_launch_workgroups(const irt_context *ctx, int numTiles, int numFrames);
+/* The same bound without a context or a device: for `variant` (one that is not compiled counts as
+ * the default), with measured-cost scheduling on (sched != 0) or off. */
+long long irt_debug_variant_workgroups(int variant, int sched, int numTiles, int numFrames);
+/* The launch plan (no context, no device): the kernel and grid a launch of `variant` gets whose
+ * arguments say this -- sampler (IRT_MODE_*), accelMode (IRT_ACCEL_*), numTiles 64x64 tiles x
+ * numFrames frames, numSplit measured-cost work items, rows of voidLive + voidRow void work items,
+ * queueWG resident workgroups for a persistent launch, and in `flags` which of the slot table, the
+ * void bitmap, the void work-item list and the persistent queue the arguments carry, and whether
+ * the frames are chained.  A form the variant does not have is passed over, as in a launch.
+ * out = {the kernel's template argument (k_render<id>), threads per workgroup, grid x, grid y,
+ * k_accumulate's blocks}.  IRT_E_INVALID for a variant that is not compiled. */
+enum {
+  IRT_DEBUG_PLAN_SLOTS = 1,
+  IRT_DEBUG_PLAN_VOID_BITS = 2,
+  IRT_DEBUG_PLAN_VOID_LIST = 4,
+  IRT_DEBUG_PLAN_QUEUE = 8,
+  IRT_DEBUG_PLAN_CHAIN = 16
+};
+int irt_debug_plan(int variant, int sampler, int accelMode, int flags, int numTiles, int numFrames,
+                   uint32_t numSplit, uint32_t voidLive, uint32_t voidRow, int queueWG, int out[5]);
+/* The same five numbers for the context's last launch, as it was planned (also for a launch without
+ * tiles, which dispatches nothing); zeros before the first launch. */
+int irt_debug_last_plan(const irt_context *ctx, int out[5]);
 /* Measured-cost scheduling (IRT_SCHED; on by default for scenes with holes): the last launch's
  * split WORK ITEMS in *numSplit -- every split packet (one longer than IRT_SPLIT_FACTOR (0.35 with holes, else 1) x
  * the frame's ideal span, the packets' durations over the resident slots) is rendered first in
