@@ -226,7 +226,8 @@ struct irt_context {
   hipEvent_t evSample = nullptr;
   bool samplePending = false;       // evSample is recorded and not yet waited for
   hipStream_t sampleStream = nullptr;  // stream of the previous sampling call
-  // irt_sample_latlon's tables {cos, sin} x numLat, {cos, sin} x numLon, radius x numLevels: the
+  // The sampling calls' tables (irt_sample_latlon: {cos, sin} x numLat, {cos, sin} x numLon, radius x
+  // numLevels; irt_column_latlon: the same and the weights; irt_render_column: radii, weights): the
   // device copy the kernel reads and the pinned staging its upload comes from (both grow when a
   // grid needs more floats); evSampleTab, behind the upload, says when the staging is free again
   float *d_sampleTab = nullptr, *h_sampleTab = nullptr;
@@ -302,7 +303,7 @@ namespace irt {
 // and the caller's buffers -- the camera, accumID and its lerp weight, the ambient terms, the
 // classification and the pixel write -- as every render launch fills them (fill_args)
 void frame_args(const irt_context *c, const irt_launch_params *lp, uint32_t *fb, irt_vec4f *accum, RenderArgs &A);
-// irt_sample.hip: what the sampling calls (irt_sample.hip, irt_levels.hip) share on the host.
+// irt_sample.hip: what the sampling calls (irt_sample.hip, irt_levels.hip, irt_column.hip) share on the host.
 // scene_args zeroes A and fills the scene side of a sampling launch's arguments; sample_check is
 // the checks every sampling call makes before it touches the device; sample_begin takes the call's
 // place behind the previous sampling call before anything is queued on `s`, sample_end marks its
@@ -311,4 +312,9 @@ void scene_args(const irt_context *c, int mode, RenderArgs &A);
 int sample_check(const irt_context *c, int mode, const char *what);
 int sample_begin(irt_context *c, hipStream_t s);
 int sample_end(irt_context *c, hipStream_t s);
+// ... and the calls that pass tables (d_sampleTab): sample_tab_reserve, after sample_begin, leaves
+// the pinned staging free and both copies at least `need` floats long; the call fills the staging;
+// sample_tab_upload queues its first `need` floats into the device copy on `s`
+int sample_tab_reserve(irt_context *c, size_t need);
+int sample_tab_upload(irt_context *c, size_t need, hipStream_t s);
 }  // namespace irt

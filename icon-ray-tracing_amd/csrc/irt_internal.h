@@ -129,6 +129,12 @@ int latlon_args(const char *what, const float *lat, int numLat, const float *lon
 int levels_args(const char *what, const float *radius, int numLevels);
 void levels_order(const float *radius, int numLevels, float *sorted, int32_t *index);
 
+// Column products (host/irt_column.cpp; csrc/irt_column.hip): the check of the weights (NULL, or
+// numLevels finite floats), and irt_render_column's check of its levels (numLevels >= 1, every
+// radius finite and positive, then the weights).  The reduction itself is csrc/irt_column.h.
+int column_weights(const char *what, const float *weight, int numLevels);
+int column_levels_args(const char *what, const float *radius, const float *weight, int numLevels);
+
 // Measured-cost scheduling (host/irt_sched.cpp): the words of one order buffer from the measured
 // costs of a frame's packets (cost: 4 per 256-pixel block, 64 per 64x64 tile).  out holds
 //   [0, cap)                    the block order: tiles, or bands of max(1, tilesX / tileStride)

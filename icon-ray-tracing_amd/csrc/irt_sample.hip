@@ -99,6 +99,47 @@ int sample_end(irt_context *c, hipStream_t s) {
   return IRT_OK;
 }
 
+// The sampling calls' tables (irt_context.h d_sampleTab): before a call fills the pinned staging
+// with `need` floats -- the previous call's upload has left it, and both copies hold that many,
+// grown on demand
+int sample_tab_reserve(irt_context *c, size_t need) {
+  int rc;
+  if (!c->evSampleTab) IRT_HIP(hipEventCreateWithFlags(&c->evSampleTab, hipEventDisableTiming));
+  if (c->sampleTabBusy) {  // the previous call's upload still reads the staging
+    IRT_HIP(hipEventSynchronize(c->evSampleTab));
+    c->sampleTabBusy = false;
+  }
+  if (need > c->sampleTabCap) {
+    IRT_HIP(wait_samples(c));  // an earlier grid's kernel may still read the device copy
+    if (c->d_sampleTab) {
+      IRT_HIP(hipFree(c->d_sampleTab));
+      c->d_sampleTab = nullptr;
+      c->bytes -= c->sampleTabCap * sizeof(float);
+    }
+    if (c->h_sampleTab) {
+      IRT_HIP(hipHostFree(c->h_sampleTab));
+      c->h_sampleTab = nullptr;
+    }
+    c->sampleTabCap = 0;
+    c->info.deviceBytes = c->bytes;
+    const size_t cap = std::max<size_t>(need + need / 2, 4096);
+    IRT_HIP(hipHostMalloc((void **)&c->h_sampleTab, cap * sizeof(float)));
+    if ((rc = dalloc(c, &c->d_sampleTab, cap))) return rc;  // (the staging stays, with capacity 0: the next
+                                                            // call frees it and allocates both anew)
+    c->sampleTabCap = cap;
+    c->info.deviceBytes = c->bytes;
+  }
+  return IRT_OK;
+}
+// ... and after it: the staging's first `need` floats into the device copy on `s`, behind every
+// earlier sampling kernel (same stream: stream order; another: sample_begin's wait)
+int sample_tab_upload(irt_context *c, size_t need, hipStream_t s) {
+  IRT_HIP(hipMemcpyAsync(c->d_sampleTab, c->h_sampleTab, need * sizeof(float), hipMemcpyHostToDevice, s));
+  IRT_HIP(hipEventRecord(c->evSampleTab, s));
+  c->sampleTabBusy = true;
+  return IRT_OK;
+}
+
 namespace {
 
 // One located point's outputs: streaming stores (nobody re-reads them in this kernel), as the
@@ -245,40 +286,13 @@ int irt_sample_latlon(irt_context *c, int mode, const float *lat, int numLat, co
   if (total == 0) return IRT_OK;
   hipStream_t s = (hipStream_t)stream;
   if ((rc = sample_begin(c, s))) return rc;
-  // the tables: through the context's pinned staging into its device copy, both grown on demand
+  // the tables: through the context's pinned staging into its device copy
   const size_t need = 2 * (size_t)numLat + 2 * (size_t)numLon + (size_t)numLevels;
-  if (!c->evSampleTab) IRT_HIP(hipEventCreateWithFlags(&c->evSampleTab, hipEventDisableTiming));
-  if (c->sampleTabBusy) {  // the previous call's upload still reads the staging
-    IRT_HIP(hipEventSynchronize(c->evSampleTab));
-    c->sampleTabBusy = false;
-  }
-  if (need > c->sampleTabCap) {
-    IRT_HIP(wait_samples(c));  // an earlier grid's kernel may still read the device copy
-    if (c->d_sampleTab) {
-      IRT_HIP(hipFree(c->d_sampleTab));
-      c->d_sampleTab = nullptr;
-      c->bytes -= c->sampleTabCap * sizeof(float);
-    }
-    if (c->h_sampleTab) {
-      IRT_HIP(hipHostFree(c->h_sampleTab));
-      c->h_sampleTab = nullptr;
-    }
-    c->sampleTabCap = 0;
-    c->info.deviceBytes = c->bytes;
-    const size_t cap = std::max<size_t>(need + need / 2, 4096);
-    IRT_HIP(hipHostMalloc((void **)&c->h_sampleTab, cap * sizeof(float)));
-    if ((rc = dalloc(c, &c->d_sampleTab, cap))) return rc;  // (the staging stays, with capacity 0: the next
-                                                            // call frees it and allocates both anew)
-    c->sampleTabCap = cap;
-    c->info.deviceBytes = c->bytes;
-  }
+  if ((rc = sample_tab_reserve(c, need))) return rc;
   float *latCS = c->h_sampleTab, *lonCS = latCS + 2 * (size_t)numLat, *rad = lonCS + 2 * (size_t)numLon;
   latlon_trig(lat, numLat, lon, numLon, latCS, lonCS);
   memcpy(rad, radius, (size_t)numLevels * sizeof(float));
-  // behind every earlier sampling kernel (same stream: stream order; another: sample_begin's wait)
-  IRT_HIP(hipMemcpyAsync(c->d_sampleTab, c->h_sampleTab, need * sizeof(float), hipMemcpyHostToDevice, s));
-  IRT_HIP(hipEventRecord(c->evSampleTab, s));
-  c->sampleTabBusy = true;
+  if ((rc = sample_tab_upload(c, need, s))) return rc;
 
   RenderArgs A;
   scene_args(c, mode, A);

@@ -1,5 +1,5 @@
 // irt_sample_dev.h -- the device half the sampling translation units share (irt_sample.hip: points
-// and lat/lon grids; irt_levels.hip: level surfaces): the guard in front of the locator, a one-wave
+// and lat/lon grids; irt_levels.hip: level surfaces; irt_column.hip: column products): the guard in front of the locator, a one-wave
 // workgroup's LDS, sampleVolume of one wave's 64 points, and the sampling grids' workgroup index.
 // Their host half (scene_args, sample_check, sample_begin, sample_end) is declared in irt_context.h.
 //

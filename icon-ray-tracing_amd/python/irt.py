@@ -34,6 +34,7 @@ MODE_TRIANGLES = 1     # closest bottom triangle toward the centre (deviceCode.c
 MODE_CUBQL = 2         # wedges + intersectWedgeEXT (deviceCode.cu:90-115)
 MAX_LEVELS = 16        # IRT_MAX_LEVELS: the most radii of one render_levels call
 LEVELS_BACK = 1        # IRT_LEVELS_BACK: also the far-side hits of spheres the camera is outside of
+COLUMN_WSUM, COLUMN_MAX, COLUMN_MIN = 0, 1, 2  # IRT_COLUMN_*: the product render_column shows
 # The raygen's render variants (irt_kernels.h OPT_* bits), all bit-identical: the product
 # library compiles 73405728 (the default: one-wave workgroups since round 4, 5 waves/SIMD; since
 # round 5 with the miss mode, the LDS-DMA prologue tables and the DPP prefix, and 73667872 its
@@ -117,6 +118,15 @@ class RenderStats(C.Structure):
 _lib = None
 
 
+class ColumnOut(C.Structure):
+    """irt_column_out: where each output of a column reduction goes (0: not written)."""
+    _fields_ = [(n, C.c_void_p) for n in ("wsum", "vmax", "vmin", "kmax", "kmin", "count")]
+
+
+COLUMN_OUTPUTS = {"wsum": np.float32, "vmax": np.float32, "vmin": np.float32,
+                  "kmax": np.int32, "kmin": np.int32, "count": np.int32}
+
+
 def lib() -> C.CDLL:
     """Load the in-tree product library (fails loudly if it was not built)."""
     global _lib
@@ -156,6 +166,9 @@ def lib() -> C.CDLL:
             "irt_latlon_points": [P, I, P, I, P, I, P],
             "irt_render_levels": [P, C.POINTER(LaunchParams), I, I, P, I, I, P, P, P, P, F, P],
             "irt_levels_order": [P, I, P, P],
+            "irt_column_reduce": [P, P, I, S, P, F, ColumnOut],
+            "irt_column_latlon": [P, I, P, I, P, I, P, P, I, ColumnOut, F, P],
+            "irt_render_column": [P, C.POINTER(LaunchParams), I, I, F, P, P, I, I, P, P, P, F, P],
             "irt_debug_sample_admits": [F, F, F],
             "irt_clear_frame": [P, P, P, S, P],
             "irt_render": [P, C.POINTER(LaunchParams), I, I, P, P, P],
@@ -253,6 +266,34 @@ def levels_order(radii):
     out, idx = np.zeros(r.size, np.float32), np.zeros(r.size, np.int32)
     _check(lib().irt_levels_order(_ptr(r), r.size, _ptr(out), _ptr(idx)), "irt_levels_order")
     return out, idx
+
+
+def _weights(weight, levels: int):
+    """A column call's weights: None, or `levels` float32."""
+    if weight is None:
+        return None
+    w = np.ascontiguousarray(weight, dtype=np.float32).reshape(-1)
+    if w.size != levels:
+        raise IrtError(f"{w.size} weights for {levels} levels", E_INVALID)
+    return w
+
+
+def column_reduce(value, found, weight=None, miss: float = float("nan")) -> dict:
+    """irt_column_reduce: the column reduction of value / found (levels, ...) -- sample_latlon's
+    layout -- over the first axis, on the host: a dict of wsum, vmax, vmin (float32), kmax, kmin,
+    count (int32), each of shape value.shape[1:].  weight: None (every weight 1) or one float per
+    level.  No GPU."""
+    value = np.ascontiguousarray(value, dtype=np.float32)
+    found = np.ascontiguousarray(found, dtype=np.uint8)
+    if value.ndim < 1 or value.shape != found.shape:
+        raise IrtError(f"column_reduce: value {value.shape} and found {found.shape} differ", E_INVALID)
+    levels, shape = value.shape[0], value.shape[1:]
+    w = _weights(weight, levels)
+    out = {k: np.zeros(shape, t) for k, t in COLUMN_OUTPUTS.items()}
+    _check(lib().irt_column_reduce(_ptr(value), _ptr(found), levels, int(np.prod(shape, dtype=np.int64)),
+                                   _ptr(w) if w is not None else None, float(miss),
+                                   ColumnOut(**{k: a.ctypes.data for k, a in out.items()})), "irt_column_reduce")
+    return out
 
 
 def vec3(v) -> Vec3:
@@ -979,6 +1020,52 @@ class Context:
                                        LEVELS_BACK if back else 0, C.c_void_p(fb_ptr), C.c_void_p(accum_ptr),
                                        C.c_void_p(value_ptr), C.c_void_p(level_ptr), float(miss),
                                        C.c_void_p(stream)), "irt_render_levels")
+
+    def column_latlon(self, lat, lon, radius, out: dict, weight=None, mode: int = MODE_USER_GEOM,
+                      miss: float = float("nan"), stream: int = 0):
+        """irt_column_latlon: the column reduction (column_reduce) over the levels `radius` of the grid
+        sample_latlon samples, in one pass: `out` maps any of wsum, vmax, vmin (float32), kmax, kmin,
+        count (int32) to a device pointer of len(lat) * len(lon) elements, column (j, i) at
+        [j * len(lon) + i].  weight: None or one float per level.  Returns (lat, lon) sizes."""
+        lat, lon, radius = _latlon_arrays(lat, lon, radius)
+        w = _weights(weight, radius.size)
+        unknown = set(out) - set(COLUMN_OUTPUTS)
+        if unknown:
+            raise IrtError(f"column_latlon: unknown outputs {sorted(unknown)}", E_INVALID)
+        _check(lib().irt_column_latlon(self._h, int(mode), _ptr(lat), lat.size, _ptr(lon), lon.size, _ptr(radius),
+                                       _ptr(w) if w is not None else None, radius.size,
+                                       ColumnOut(**{k: int(v) or None for k, v in out.items()}), float(miss),
+                                       C.c_void_p(stream)), "irt_column_latlon")
+        return lat.size, lon.size
+
+    def column(self, lat, lon, radius, weight=None, mode: int = MODE_USER_GEOM, miss: float = float("nan")) -> dict:
+        """The column products on a lat x lon grid: a dict of torch tensors wsum, vmax, vmin
+        (float32), kmax, kmin, count (int32) of shape (len(lat), len(lon)) on the context's device,
+        computed on torch's current stream."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        shape = (np.size(lat), np.size(lon))
+        with torch.cuda.device(dev):
+            out = {k: torch.empty(shape, dtype=torch.float32 if t is np.float32 else torch.int32, device=dev)
+                   for k, t in COLUMN_OUTPUTS.items()}
+            self.column_latlon(lat, lon, radius, {k: t.data_ptr() for k, t in out.items()}, weight, mode, miss,
+                               torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
+    def render_column(self, lp: LaunchParams, width: int, height: int, surface_radius: float, radii, fb_ptr: int,
+                      accum_ptr: int, value_ptr: int = 0, weight=None, product: int = COLUMN_WSUM,
+                      miss: float = float("nan"), stream: int = 0):
+        """irt_render_column: a column product (COLUMN_WSUM, COLUMN_MAX or COLUMN_MIN over the levels
+        `radii`, any number of them) drawn on the sphere of surface_radius as lp's camera sees it,
+        through the transfer function, into fb / accum (device arrays of width * height, as
+        render_levels'); value_ptr (float32) takes the product per pixel, 0: not written.  lp.mode
+        chooses the sampler.  Enqueued on `stream`."""
+        radii = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+        w = _weights(weight, radii.size)
+        _check(lib().irt_render_column(self._h, C.byref(lp), int(width), int(height), float(surface_radius),
+                                       _ptr(radii), _ptr(w) if w is not None else None, radii.size, int(product),
+                                       C.c_void_p(fb_ptr), C.c_void_p(accum_ptr), C.c_void_p(value_ptr), float(miss),
+                                       C.c_void_p(stream)), "irt_render_column")
 
     def resample(self, points, mode: int = MODE_USER_GEOM, miss: float = float("nan")):
         """The field at `points` (..., 3): a float32 torch tensor on the context's device (sampled

@@ -295,6 +295,75 @@ int irt_render_levels(irt_context *ctx, const irt_launch_params *lp, int width, 
  * [1, IRT_MAX_LEVELS], a radius that is not finite and positive, or a NULL pointer. */
 int irt_levels_order(const float *radius, int numLevels, float *sorted, int32_t *index);
 
+/* ---------------------------------------------------------------- column products
+ * A reduction over the vertical of the field sampled on a column's levels: the weighted sum
+ * ("total column X"), the maximum and the minimum with the levels they sit at, and how many of the
+ * levels hold data -- on a lat x lon grid (irt_column_latlon) and on the globe as the camera sees
+ * it (irt_render_column).  One pass on the device: the numLevels values per column that
+ * irt_sample_latlon would write never reach memory.  No counterpart in the reference.
+ *
+ * The reduction of one column walks the levels k = 0 .. numLevels-1 in ascending order and skips a
+ * level that was not found.  At the first found level, with value v: mn = mx = v, kmin = kmax = k,
+ * wsum = weight[k] * v.  At each later found level: if (v < mn) { mn = v; kmin = k; } if (v > mx)
+ * { mx = v; kmax = k; } wsum = wsum + weight[k] * v.  count++ at every found level.  The
+ * comparisons are strict: a tie keeps the lower k, a NaN never replaces a value.  Everything is
+ * float, one multiply then one add, never an fma.  weight == NULL: every weight is 1.0f (1.0f * v is
+ * v, so wsum is the plain sequential sum).  A column with count == 0 has wsum = vmax = vmin =
+ * missValue and kmax = kmin = -1. */
+typedef struct irt_column_out {      /* every pointer may be NULL: that output is not written */
+  float   *wsum;    /* sum over found levels of weight[k] * value, in level order */
+  float   *vmax, *vmin;
+  int32_t *kmax, *kmin;   /* level index of the max / min, or -1 */
+  int32_t *count;         /* found levels */
+} irt_column_out;
+/* Host helper, no GPU: the reduction above of numColumns columns whose level k is at value / found
+ * [k * numColumns + c] (the layout irt_sample_latlon writes, with numColumns = numLat * numLon);
+ * out's arrays hold numColumns elements.  IRT_E_INVALID for numLevels < 1, and for a NULL value or
+ * found with columns to reduce. */
+int irt_column_reduce(const float *value, const uint8_t *found, int numLevels, size_t numColumns,
+                      const float *weight, float missValue, irt_column_out out);
+/* The reduction on the grid of irt_sample_latlon: point (k, j, i) is exactly irt_sample_latlon's
+ * point (k, j, i) for the same lat, lon and radius, and column (j, i) writes its results at
+ * [j*numLon + i] of the DEVICE arrays in d_out.  Equal, bit for bit, to irt_column_reduce applied to
+ * irt_sample_latlon's output for the same arguments, for every sampler.
+ *  - lat, lon, radius, weight: HOST arrays, copied before the call returns; weight is NULL or
+ *    numLevels floats.  The radii may come in any order and may repeat: k is the caller's index,
+ *    and the sum runs in that order.
+ *  - A sampling call in every respect of "resampling" above: mode, ordering, no statistics, no
+ *    IRT_E_CHAIN.
+ *  - IRT_E_INVALID, nothing written: what irt_sample_latlon refuses for these arguments, and a
+ *    weight that is not finite.  A grid without points (a zero count), or a d_out whose pointers
+ *    are all NULL: IRT_OK, nothing launched. */
+int irt_column_latlon(irt_context *ctx, int mode, const float *lat, int numLat, const float *lon,
+                      int numLon, const float *radius, const float *weight, int numLevels,
+                      irt_column_out d_out, float missValue, void *stream);
+/* The product on the globe: the shell is ~75 km thick on a 6,371 km globe, so a column product
+ * mapped onto a sphere is the readable 2-D view of the volume.  Per pixel:
+ *  - the ray and the single hit slot of irt_render_levels with the one level surfaceRadius and
+ *    flags 0: the near hit when tn > 0, else the far hit when tf > 0 (the camera is inside);
+ *  - with P = org + dir * t: len = sqrtf(P.x*P.x + P.y*P.y + P.z*P.z), summed left to right, and the
+ *    column point of level k is (P.x*s, P.y*s, P.z*s) with s = radius[k] / len, sampled exactly as
+ *    a point of irt_sample_points;
+ *  - the reduction above; v = the chosen product (wsum, vmax or vmin);
+ *  - a pixel with count > 0: s4 = postClassify(v), a = clamp(s4.w, 0, 1), C = a * ((s4.rgb *
+ *    ambientColor) * ambientRadiance), A = a.  A pixel without a live hit, or with count == 0: C =
+ *    A = 0 and v = missValue;
+ *  - (C, A) is lerped into accum and fb written as irt_render_levels writes every pixel; d_value[p]
+ *    = v (d_value may be NULL).
+ * Of lp the call uses what irt_render_levels uses.  Ordering: as irt_render_levels (a sampling
+ * call; against irt_render* on the same d_fb / d_accum ordered only by its stream).
+ * IRT_E_INVALID, nothing written: what irt_render_levels refuses (numLevels < 1 in place of its
+ * range: there is no upper limit here), a surfaceRadius that is not finite and positive, a product
+ * that is none of the three, a weight that is not finite.
+ * The tile forms, multi-GPU splitting and several frames per launch have no column form. */
+#define IRT_COLUMN_WSUM 0
+#define IRT_COLUMN_MAX 1
+#define IRT_COLUMN_MIN 2
+int irt_render_column(irt_context *ctx, const irt_launch_params *lp, int width, int height,
+                      float surfaceRadius, const float *radius, const float *weight, int numLevels,
+                      int product, uint32_t *d_fb, irt_vec4f *d_accum, float *d_value,
+                      float missValue, void *stream);
+
 /* == clearFramebuffer (common/pipeline.cu:171-199): fb = make_rgba(0), accum = 0. */
 int irt_clear_frame(irt_context *ctx, uint32_t *d_fb, irt_vec4f *d_accum, size_t numPixels,
                     void *stream);
