@@ -135,6 +135,15 @@ void levels_order(const float *radius, int numLevels, float *sorted, int32_t *in
 int column_weights(const char *what, const float *weight, int numLevels);
 int column_levels_args(const char *what, const float *radius, const float *weight, int numLevels);
 
+// Sections (host/irt_section.cpp; csrc/irt_section.hip): the columns' trig table, {cosf lat, sinf lat,
+// cosf lon, sinf lon} per (lat, lon) pair from the host's glibc, and the check irt_section and
+// irt_section_points share (negative counts, more than kSampleMaxPoints points, a NULL array with
+// points to sample); *total = numColumns * numLevels
+constexpr size_t kSectionTrigSplit = 1 << 14;  // columns from which section_trig uses default_threads()
+void section_trig(const float *lat, const float *lon, int numColumns, float *tab);
+int section_args(const char *what, const float *lat, const float *lon, int numColumns, const float *radius,
+                 int numLevels, size_t *total);
+
 // Measured-cost scheduling (host/irt_sched.cpp): the words of one order buffer from the measured
 // costs of a frame's packets (cost: 4 per 256-pixel block, 64 per 64x64 tile).  out holds
 //   [0, cap)                    the block order: tiles, or bands of max(1, tilesX / tileStride)

@@ -22,6 +22,13 @@
 //                                                irt_render_levels; one device)
 //           [--levels-back]                     (... with the far sides of spheres the camera
 //                                                is outside of, IRT_LEVELS_BACK)
+//           [--section lat0,lon0,lat1,lon1,n --section-levels r0,r1,...]
+//                                               (the vertical cross-section along the great circle
+//                                                between two points, degrees, on n columns and the
+//                                                levels of these radii, metres from the centre, in
+//                                                place of the frame: irt_section; one device; the
+//                                                curtain goes to icon_rt_section.png, the last level
+//                                                in the top row, and raw to --dump-fb, row k = level k)
 
 #include <math.h>
 #include <stdio.h>
@@ -58,7 +65,17 @@ struct AppState {  // hostCode.cu:65-92 (the parts this backend uses)
   std::string dumpFb;
   std::vector<float> levels;         // --levels: irt_render_levels in place of irt_render
   bool levelsBack = false;
+  std::vector<float> section;        // --section: lat0, lon0, lat1, lon1 (degrees), n
+  std::vector<float> sectionLevels;  // --section-levels
 } g;
+
+void parseList(const std::string &list, std::vector<float> &out) {
+  for (size_t a = 0; a < list.size();) {
+    const size_t b = std::min(list.find(',', a), list.size());
+    out.push_back(strtof(list.substr(a, b - a).c_str(), nullptr));
+    a = b + 1;
+  }
+}
 
 bool endsWith(const std::string &s, const std::string &suffix) {
   return s.size() >= suffix.size() && s.compare(s.size() - suffix.size(), suffix.size(), suffix) == 0;
@@ -96,15 +113,14 @@ void parseCommandLine(int argc, char *argv[]) {  // hostCode.cu:106-129
       g.gpus = atoi(argv[++i]);
     else if (arg == "--dump-fb" && i + 1 < argc)
       g.dumpFb = argv[++i];
-    else if (arg == "--levels" && i + 1 < argc) {
-      const std::string list = argv[++i];
-      for (size_t a = 0; a < list.size();) {
-        const size_t b = std::min(list.find(',', a), list.size());
-        g.levels.push_back(strtof(list.substr(a, b - a).c_str(), nullptr));
-        a = b + 1;
-      }
-    } else if (arg == "--levels-back")
+    else if (arg == "--levels" && i + 1 < argc)
+      parseList(argv[++i], g.levels);
+    else if (arg == "--levels-back")
       g.levelsBack = true;
+    else if (arg == "--section" && i + 1 < argc)
+      parseList(argv[++i], g.section);
+    else if (arg == "--section-levels" && i + 1 < argc)
+      parseList(argv[++i], g.sectionLevels);
   }
 }
 
@@ -129,6 +145,18 @@ int main(int argc, char *argv[]) {
   if (!g.levels.empty() && (g.gpus > 0 || g.benchFrames > 0)) {
     fprintf(stderr, "icon_rt: --levels renders on one device and has no --bench form\n");
     return -1;
+  }
+  if (!g.section.empty() || !g.sectionLevels.empty()) {
+    if (g.gpus > 0 || g.benchFrames > 0) {
+      fprintf(stderr, "icon_rt: --section runs on one device and has no --bench form\n");
+      return -1;
+    }
+    if (g.section.size() != 5 || g.sectionLevels.empty() || !(g.section[4] >= 1.f && g.section[4] < 2147483648.f) ||
+        !g.levels.empty()) {
+      fprintf(stderr, "icon_rt: --section takes lat0,lon0,lat1,lon1,n (degrees; n >= 1) with --section-levels "
+                      "r0,r1,... and without --levels\n");
+      return -1;
+    }
   }
 
   // load (hostCode.cu:717-734) or synthesise
@@ -222,6 +250,40 @@ int main(int argc, char *argv[]) {
     lp.mode = g.mode;
   } else if (g.mode != IRT_MODE_USER_GEOM) {
     fprintf(stderr, "icon_rt: unknown -mode %d; using the cell sampler (-mode 0)\n", g.mode);
+  }
+
+  if (!g.section.empty()) {  // the curtain in place of the frame loop: an image of its own
+    const Transfunc *tf = pl.getTransfunc(0);
+    if (irt_set_transfunc(ctx, tf->lut.data(), tf->size(), tf->valueRange, tf->opacity)) die("irt_set_transfunc");
+    const int nCol = (int)g.section[4], nLev = (int)g.sectionLevels.size();
+    const double rad = 3.14159265358979323846 / 180.0;
+    std::vector<float> lat(nCol), lon(nCol);
+    double arc = 0.0;
+    if (irt_great_circle((float)(g.section[0] * rad), (float)(g.section[1] * rad), (float)(g.section[2] * rad),
+                         (float)(g.section[3] * rad), nCol, lat.data(), lon.data(), &arc))
+      die("irt_great_circle");
+    const size_t nPix = (size_t)nCol * nLev;
+    irt_section_out out;
+    memset(&out, 0, sizeof(out));
+    if (hipMalloc((void **)&out.rgba, nPix * 4) != hipSuccess) die("hipMalloc");
+    if (irt_section(ctx, lp.mode, lat.data(), lon.data(), nCol, g.sectionLevels.data(), nullptr, nLev, lp.ambientColor,
+                    lp.ambientRadiance, out, 0.f, nullptr))
+      die("irt_section");
+    std::vector<uint32_t> h(nPix);
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(h.data(), out.rgba, nPix * 4, hipMemcpyDeviceToHost) != hipSuccess)
+      die("section copy");
+    (void)hipFree(out.rgba);
+    const std::string fileName = pl.name + "_section.png";
+    if (!writePNG(fileName, h.data(), nCol, nLev, /*flip*/ true)) die("section write");
+    printf("Output: %s (%d columns over %.6f rad x %d levels)\n", fileName.c_str(), nCol, arc, nLev);
+    if (!g.dumpFb.empty()) {  // raw: [k * n + c], RGBA8 with r in the low byte
+      FILE *f = fopen(g.dumpFb.c_str(), "wb");
+      if (!f || fwrite(h.data(), 4, h.size(), f) != h.size()) die("dump-fb write");
+      fclose(f);
+    }
+    irt_destroy(ctx);
+    return 0;
   }
 
   pl.clearFramebuffer = [&] {

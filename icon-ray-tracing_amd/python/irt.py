@@ -127,6 +127,14 @@ COLUMN_OUTPUTS = {"wsum": np.float32, "vmax": np.float32, "vmin": np.float32,
                   "kmax": np.int32, "kmin": np.int32, "count": np.int32}
 
 
+class SectionOut(C.Structure):
+    """irt_section_out: where each output of a section goes (0: not written)."""
+    _fields_ = [("value", C.c_void_p), ("found", C.c_void_p), ("rgba", C.c_void_p), ("column", ColumnOut)]
+
+
+SECTION_OUTPUTS = {"value": np.float32, "found": np.uint8, "rgba": np.uint32}  # per point; COLUMN_OUTPUTS per column
+
+
 def lib() -> C.CDLL:
     """Load the in-tree product library (fails loudly if it was not built)."""
     global _lib
@@ -169,6 +177,9 @@ def lib() -> C.CDLL:
             "irt_column_reduce": [P, P, I, S, P, F, ColumnOut],
             "irt_column_latlon": [P, I, P, I, P, I, P, P, I, ColumnOut, F, P],
             "irt_render_column": [P, C.POINTER(LaunchParams), I, I, F, P, P, I, I, P, P, P, F, P],
+            "irt_section": [P, I, P, P, I, P, P, I, Vec3, F, SectionOut, F, P],
+            "irt_section_points": [P, P, I, P, I, P],
+            "irt_great_circle": [F, F, F, F, I, P, P, C.POINTER(C.c_double)],
             "irt_debug_sample_admits": [F, F, F],
             "irt_clear_frame": [P, P, P, S, P],
             "irt_render": [P, C.POINTER(LaunchParams), I, I, P, P, P],
@@ -470,6 +481,37 @@ def latlon_points(lat, lon, radius) -> np.ndarray:
     _check(lib().irt_latlon_points(_ptr(lat), lat.size, _ptr(lon), lon.size, _ptr(radius),
                                    radius.size, _ptr(xyz)), "irt_latlon_points")
     return xyz
+
+
+def _section_arrays(lat, lon, radius):
+    lat, lon, radius = _latlon_arrays(lat, lon, radius)
+    if lat.size != lon.size:
+        raise IrtError(f"a section's columns are (lat, lon) pairs: {lat.size} lat for {lon.size} lon", E_INVALID)
+    return lat, lon, radius
+
+
+def section_points(lat, lon, radius) -> np.ndarray:
+    """irt_section_points: the points Context.section samples, float32 of shape (len(radius),
+    len(lat), 3): toCartesian(radius[k], lat[c], lon[c]) with the host's cosf/sinf, column c being
+    the pair (lat[c], lon[c]) (radians; radius in metres from the Earth's centre).  No GPU."""
+    lat, lon, radius = _section_arrays(lat, lon, radius)
+    xyz = np.zeros((radius.size, lat.size, 3), np.float32)
+    _check(lib().irt_section_points(_ptr(lat), _ptr(lon), lat.size, _ptr(radius), radius.size, _ptr(xyz)),
+           "irt_section_points")
+    return xyz
+
+
+def great_circle(lat0: float, lon0: float, lat1: float, lon1: float, n: int):
+    """irt_great_circle: (lat, lon, arc) -- n points (float32, radians) along the great circle from
+    (lat0, lon0) to (lat1, lon1), the shorter way, equally spaced in angle, the end points being the
+    inputs unchanged; arc = the angle between the end points in radians (the plot's x-axis runs
+    from 0 to arc).  A polyline is joined leg by leg.  No GPU."""
+    n = int(n)
+    lat, lon = np.zeros(max(n, 0), np.float32), np.zeros(max(n, 0), np.float32)
+    arc = C.c_double()
+    _check(lib().irt_great_circle(float(lat0), float(lon0), float(lat1), float(lon1), n, _ptr(lat), _ptr(lon),
+                                  C.byref(arc)), "irt_great_circle")
+    return lat, lon, arc.value
 
 
 def sample_admits(x: float, y: float, z: float) -> bool:
@@ -1066,6 +1108,51 @@ class Context:
                                        _ptr(radii), _ptr(w) if w is not None else None, radii.size, int(product),
                                        C.c_void_p(fb_ptr), C.c_void_p(accum_ptr), C.c_void_p(value_ptr), float(miss),
                                        C.c_void_p(stream)), "irt_render_column")
+
+    def section_raw(self, lat, lon, radius, out: dict, weight=None, ambient=(1.0, 1.0, 1.0), radiance: float = 1.0,
+                    mode: int = MODE_USER_GEOM, miss: float = float("nan"), stream: int = 0):
+        """irt_section: the field on the levels `radius` of the columns at the pairs (lat[c], lon[c])
+        (host arrays, radians and metres from the centre), in one pass.  `out` maps any of value
+        (float32), found (uint8), rgba (uint32; the curtain through the transfer function, ambient
+        and radiance) -- device pointers of len(radius) * len(lat) elements, point (k, c) at
+        [k * len(lat) + c] -- and of the column outputs wsum, vmax, vmin (float32), kmax, kmin,
+        count (int32) -- len(lat) elements -- to a device pointer.  weight: None or one float per
+        level.  Enqueued on `stream`.  Returns (levels, columns)."""
+        lat, lon, radius = _section_arrays(lat, lon, radius)
+        w = _weights(weight, radius.size)
+        unknown = set(out) - set(SECTION_OUTPUTS) - set(COLUMN_OUTPUTS)
+        if unknown:
+            raise IrtError(f"section: unknown outputs {sorted(unknown)}", E_INVALID)
+        o = SectionOut(column=ColumnOut(**{k: int(v) or None for k, v in out.items() if k in COLUMN_OUTPUTS}),
+                       **{k: int(v) or None for k, v in out.items() if k in SECTION_OUTPUTS})
+        _check(lib().irt_section(self._h, int(mode), _ptr(lat), _ptr(lon), lat.size, _ptr(radius),
+                                 _ptr(w) if w is not None else None, radius.size, vec3(ambient), float(radiance), o,
+                                 float(miss), C.c_void_p(stream)), "irt_section")
+        return radius.size, lat.size
+
+    def section(self, lat, lon, radius, weight=None, image: bool = False, columns: bool = False,
+                ambient=(1.0, 1.0, 1.0), radiance: float = 1.0, mode: int = MODE_USER_GEOM,
+                miss: float = float("nan")) -> dict:
+        """The vertical cross-section along the pairs (lat[c], lon[c]) -- a great_circle track, a
+        station list -- as a dict of torch tensors on the context's device, computed on torch's
+        current stream: value (float32) and found (uint8) of shape (len(radius), len(lat)); with
+        image=True also rgba (uint8, (len(radius), len(lat), 4): row k is level k, so flip it for a
+        picture with the top level in the top row); with columns=True also wsum, vmax, vmin
+        (float32), kmax, kmin, count (int32) of shape (len(lat),)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        L, n = np.size(radius), np.size(lat)
+        tt = {np.float32: torch.float32, np.uint8: torch.uint8, np.int32: torch.int32}
+        with torch.cuda.device(dev):
+            out = {"value": torch.empty((L, n), dtype=torch.float32, device=dev),
+                   "found": torch.empty((L, n), dtype=torch.uint8, device=dev)}
+            if image:
+                out["rgba"] = torch.empty((L, n, 4), dtype=torch.uint8, device=dev)
+            if columns:
+                out.update({k: torch.empty((n,), dtype=tt[t], device=dev) for k, t in COLUMN_OUTPUTS.items()})
+            self.section_raw(lat, lon, radius, {k: t.data_ptr() for k, t in out.items()}, weight, ambient, radiance,
+                             mode, miss, torch.cuda.current_stream(dev).cuda_stream)
+        return out
 
     def resample(self, points, mode: int = MODE_USER_GEOM, miss: float = float("nan")):
         """The field at `points` (..., 3): a float32 torch tensor on the context's device (sampled

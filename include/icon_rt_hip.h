@@ -364,6 +364,67 @@ int irt_render_column(irt_context *ctx, const irt_launch_params *lp, int width, 
                       int product, uint32_t *d_fb, irt_vec4f *d_accum, float *d_value,
                       float missValue, void *stream);
 
+/* ---------------------------------------------------------------- sections
+ * The vertical cross-section ("curtain") along a track, and profiles and column products at station
+ * lists and flight or satellite tracks: the field on numLevels levels of numColumns columns at
+ * arbitrary (lat, lon) pairs, in one pass on the device.  The shell is a few pixels thick in a frame
+ * of the globe, so a curtain is an image of its own: distance along the track on one axis, the
+ * level on the other.  No counterpart in the reference.
+ *  - lat, lon (numColumns each, radians), radius (numLevels, metres from the Earth's centre) and
+ *    weight (numLevels, or NULL: every weight 1.0f) are HOST arrays, copied before the call
+ *    returns.  Column c is the pair (lat[c], lon[c]); pairs come in any order and may repeat, and so
+ *    may the radii.
+ *  - Point (k, c) = toCartesian(radius[k], lat[c], lon[c]) (ICONGrid.h:44-54) with cosf/sinf from the
+ *    host's glibc once per column: the bits irt_latlon_points gives a grid point of the same three
+ *    numbers.  irt_section_points writes that point at xyz[3*(k*numColumns + c) ...].
+ *  - value / found [k*numColumns + c] (the layout irt_column_reduce reads) equal, bit for bit,
+ *    irt_sample_points on irt_section_points' output, for every sampler.
+ *  - column (numColumns elements per array) equals irt_column_reduce(value, found, numLevels,
+ *    numColumns, weight, missValue) bit for bit: the reduction of "column products" above.
+ *  - rgba[k*numColumns + c], row k = level k: for a found value v, s = postClassify(v)
+ *    (deviceCode.cu:127-135) with the context's transfer function, a = clamp(s.w, 0, 1), C = a *
+ *    ((s.rgb * ambientColor) * ambientRadiance), and the pixel is make_rgba(linear_to_srgb(C), a)
+ *    (deviceCode.cu:336-340) -- the bytes irt_render_column's pixel write stores for (C, a) at
+ *    accumID 0 over a cleared accum; there is no accum buffer here and no lerp.  A point that was
+ *    not found gives 0.  ambientColor and ambientRadiance are read only when rgba is asked for.
+ *    Non-finite values are outside the contract, as they are for frames.
+ *  - A sampling call in every respect of "resampling" above: mode, ordering, no launch-ring slot, no
+ *    statistics, IRT_E_CHAIN neither reported nor consumed.
+ *  - IRT_E_INVALID, nothing written: what irt_sample_latlon refuses for one axis of pairs (a NULL or
+ *    still-building context, a bad mode, a pending irt_update_values*, NULL lat, lon or radius with
+ *    points to sample, a negative count, more than 2^36 points; like it, no angle or radius is
+ *    looked at); a weight that is not finite; rgba non-NULL with no transfer function set, or with a
+ *    non-finite ambientColor or ambientRadiance.  Zero columns or zero levels, or a d_out whose
+ *    pointers are all NULL: IRT_OK, nothing launched. */
+typedef struct irt_section_out {   /* DEVICE pointers; every one may be NULL: not written */
+  float    *value;   /* [k*numColumns + c] */
+  uint8_t  *found;   /* [k*numColumns + c] */
+  uint32_t *rgba;    /* [k*numColumns + c]: the curtain, row k = level k, RGBA8 as fb */
+  irt_column_out column;   /* [c] */
+} irt_section_out;
+int irt_section(irt_context *ctx, int mode, const float *lat, const float *lon, int numColumns,
+                const float *radius, const float *weight, int numLevels,
+                irt_vec3f ambientColor, float ambientRadiance,
+                irt_section_out d_out, float missValue, void *stream);
+/* Host helper, no GPU: the points irt_section samples, xyz[3*(k*numColumns + c) ...].  Refuses what
+ * irt_section refuses of these arguments, and a NULL xyz with points to write. */
+int irt_section_points(const float *lat, const float *lon, int numColumns,
+                       const float *radius, int numLevels, float *xyz);
+/* Host helper, no GPU: numPoints points along the great circle from (lat0, lon0) to (lat1, lon1)
+ * (radians), the shorter way, equally spaced in angle; computed in double, rounded to float at the
+ * end.  With a, b the end points' unit vectors and w = atan2(|a x b|, a . b): point i is at t =
+ * i/(numPoints-1), p = (sin((1-t) w) a + sin(t w) b) / sin w, lat = asin(clamp(p.z/|p|, -1, 1)), lon =
+ * atan2(p.y, p.x).  Points 0 and numPoints-1 are the inputs unchanged; numPoints == 1 gives the start
+ * point.  *arc = w when arc is non-NULL: the plot's x-axis in radians.  End points closer than
+ * sin w < 1e-9 give every point between them equal to the start.  A latitude of exactly +-pi/2 as a
+ * float lies 4.4e-8 rad past the pole: a track between two such poles is the meridian the formula
+ * gives it (lon + pi), not one chosen by the caller's lon.  The caller joins the legs of a polyline
+ * by calling it per leg.
+ * IRT_E_INVALID: numPoints < 1, a non-finite input, a NULL lat or lon, antipodal end points (sin w <
+ * 1e-9 with a . b < 0: no unique circle). */
+int irt_great_circle(float lat0, float lon0, float lat1, float lon1, int numPoints,
+                     float *lat, float *lon, double *arc);
+
 /* == clearFramebuffer (common/pipeline.cu:171-199): fb = make_rgba(0), accum = 0. */
 int irt_clear_frame(irt_context *ctx, uint32_t *d_fb, irt_vec4f *d_accum, size_t numPixels,
                     void *stream);
