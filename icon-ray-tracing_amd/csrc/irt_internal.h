@@ -144,6 +144,12 @@ void section_trig(const float *lat, const float *lon, int numColumns, float *tab
 int section_args(const char *what, const float *lat, const float *lon, int numColumns, const float *radius,
                  int numLevels, size_t *total);
 
+// Field statistics (host/irt_histogram.cpp; csrc/irt_histogram.hip): the check irt_histogram and
+// irt_histogram_cells share -- the bin and band counts, the value range, the weighting, the band edges.
+// The definition itself is csrc/irt_histogram.h.
+int hist_args(const char *what, irt_box1f valueRange, int numBins, int weighting, const float *bandEdges,
+              int numBands);
+
 // Measured-cost scheduling (host/irt_sched.cpp): the words of one order buffer from the measured
 // costs of a frame's packets (cost: 4 per 256-pixel block, 64 per 64x64 tile).  out holds
 //   [0, cap)                    the block order: tiles, or bands of max(1, tilesX / tileStride)

@@ -29,6 +29,14 @@
 //                                                place of the frame: irt_section; one device; the
 //                                                curtain goes to icon_rt_section.png, the last level
 //                                                in the top row, and raw to --dump-fb, row k = level k)
+//           [--histogram N [--histogram-thickness] [--histogram-bands r0,r1,...]]
+//                                               (the distribution of the field's values over the
+//                                                transfer function's value range in N bins, in place
+//                                                of the frame: irt_histogram; one device; counted per
+//                                                layer or, --histogram-thickness, weighted by the layer's
+//                                                thickness in 1/64 m; per altitude band between the
+//                                                ascending radii of --histogram-bands.  One line per
+//                                                band on stdout: the N counts, then the tails)
 
 #include <math.h>
 #include <stdio.h>
@@ -67,6 +75,9 @@ struct AppState {  // hostCode.cu:65-92 (the parts this backend uses)
   bool levelsBack = false;
   std::vector<float> section;        // --section: lat0, lon0, lat1, lon1 (degrees), n
   std::vector<float> sectionLevels;  // --section-levels
+  int histBins = 0;                  // --histogram: irt_histogram in place of the frame
+  bool histogram = false, histThickness = false;
+  std::vector<float> histBands;      // --histogram-bands: the band edges
 } g;
 
 void parseList(const std::string &list, std::vector<float> &out) {
@@ -121,6 +132,13 @@ void parseCommandLine(int argc, char *argv[]) {  // hostCode.cu:106-129
       parseList(argv[++i], g.section);
     else if (arg == "--section-levels" && i + 1 < argc)
       parseList(argv[++i], g.sectionLevels);
+    else if (arg == "--histogram" && i + 1 < argc) {
+      g.histogram = true;
+      g.histBins = atoi(argv[++i]);
+    } else if (arg == "--histogram-thickness")
+      g.histThickness = true;
+    else if (arg == "--histogram-bands" && i + 1 < argc)
+      parseList(argv[++i], g.histBands);
   }
 }
 
@@ -155,6 +173,17 @@ int main(int argc, char *argv[]) {
         !g.levels.empty()) {
       fprintf(stderr, "icon_rt: --section takes lat0,lon0,lat1,lon1,n (degrees; n >= 1) with --section-levels "
                       "r0,r1,... and without --levels\n");
+      return -1;
+    }
+  }
+  if (g.histogram || g.histThickness || !g.histBands.empty()) {
+    if (g.gpus > 0 || g.benchFrames > 0 || !g.levels.empty() || !g.section.empty()) {
+      fprintf(stderr, "icon_rt: --histogram runs on one device, without --bench, --levels and --section\n");
+      return -1;
+    }
+    if (!g.histogram || g.histBins < 1 || g.histBands.size() == 1) {
+      fprintf(stderr, "icon_rt: --histogram takes the number of bins (at least 1); --histogram-thickness and "
+                      "--histogram-bands r0,r1,... (at least two radii) go with it\n");
       return -1;
     }
   }
@@ -282,6 +311,39 @@ int main(int argc, char *argv[]) {
       if (!f || fwrite(h.data(), 4, h.size(), f) != h.size()) die("dump-fb write");
       fclose(f);
     }
+    irt_destroy(ctx);
+    return 0;
+  }
+
+  if (g.histogram) {  // the distribution in place of the frame loop: text on stdout
+    const Transfunc *tf = pl.getTransfunc(0);
+    const int nBands = g.histBands.empty() ? 1 : (int)g.histBands.size() - 1, nBins = g.histBins;
+    const size_t nb = (size_t)nBands * nBins, nt = (size_t)nBands * 3;
+    irt_histogram_out out;
+    memset(&out, 0, sizeof(out));
+    if (hipMalloc((void **)&out.bins, nb * 8) != hipSuccess || hipMalloc((void **)&out.tails, nt * 8) != hipSuccess ||
+        hipMalloc((void **)&out.outside, 8) != hipSuccess)
+      die("hipMalloc");
+    if (irt_histogram(ctx, tf->valueRange, nBins, g.histThickness ? IRT_HIST_THICKNESS : IRT_HIST_COUNT,
+                      g.histBands.empty() ? nullptr : g.histBands.data(), nBands, out, nullptr))
+      die("irt_histogram");
+    std::vector<uint64_t> bins(nb), tails(nt);
+    uint64_t outside = 0;
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(bins.data(), out.bins, nb * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(tails.data(), out.tails, nt * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&outside, out.outside, 8, hipMemcpyDeviceToHost) != hipSuccess)
+      die("histogram copy");
+    (void)hipFree(out.bins), (void)hipFree(out.tails), (void)hipFree(out.outside);
+    printf("histogram: %d bins over [%.9g, %.9g], %s, %d band(s)\n", nBins, (double)tf->valueRange.lower,
+           (double)tf->valueRange.upper, g.histThickness ? "thickness in 1/64 m" : "count", nBands);
+    for (int b = 0; b < nBands; ++b) {
+      printf("band %d:", b);
+      for (int k = 0; k < nBins; ++k) printf(" %llu", (unsigned long long)bins[(size_t)b * nBins + k]);
+      printf(" | under %llu over %llu nonfinite %llu\n", (unsigned long long)tails[3 * b],
+             (unsigned long long)tails[3 * b + 1], (unsigned long long)tails[3 * b + 2]);
+    }
+    printf("outside: %llu\n", (unsigned long long)outside);
     irt_destroy(ctx);
     return 0;
   }

@@ -135,6 +135,17 @@ class SectionOut(C.Structure):
 SECTION_OUTPUTS = {"value": np.float32, "found": np.uint8, "rgba": np.uint32}  # per point; COLUMN_OUTPUTS per column
 
 
+class HistogramOut(C.Structure):
+    """irt_histogram_out: where bins, tails and outside go (0: not written); uint64 each."""
+    _fields_ = [(n, C.c_void_p) for n in ("bins", "tails", "outside")]
+
+
+HISTOGRAM_OUTPUTS = ("bins", "tails", "outside")
+HIST_COUNT, HIST_THICKNESS = 0, 1  # IRT_HIST_*
+HIST_WEIGHTINGS = {"count": HIST_COUNT, "thickness": HIST_THICKNESS}
+HIST_MAX_BINS, HIST_MAX_BANDS = 4096, 64
+
+
 def lib() -> C.CDLL:
     """Load the in-tree product library (fails loudly if it was not built)."""
     global _lib
@@ -180,6 +191,8 @@ def lib() -> C.CDLL:
             "irt_section": [P, I, P, P, I, P, P, I, Vec3, F, SectionOut, F, P],
             "irt_section_points": [P, P, I, P, I, P],
             "irt_great_circle": [F, F, F, F, I, P, P, C.POINTER(C.c_double)],
+            "irt_histogram": [P, Box1, I, I, P, I, HistogramOut, P],
+            "irt_histogram_cells": [P, S, Box1, I, I, P, I, HistogramOut],
             "irt_debug_sample_admits": [F, F, F],
             "irt_clear_frame": [P, P, P, S, P],
             "irt_render": [P, C.POINTER(LaunchParams), I, I, P, P, P],
@@ -304,6 +317,36 @@ def column_reduce(value, found, weight=None, miss: float = float("nan")) -> dict
     _check(lib().irt_column_reduce(_ptr(value), _ptr(found), levels, int(np.prod(shape, dtype=np.int64)),
                                    _ptr(w) if w is not None else None, float(miss),
                                    ColumnOut(**{k: a.ctypes.data for k, a in out.items()})), "irt_column_reduce")
+    return out
+
+
+def _hist_args(weighting, band_edges):
+    """A histogram call's weighting (a name or an IRT_HIST_* number) and band edges (None: one band;
+    else at least two float32 edges) as the library takes them: (weighting, edges or None, bands)."""
+    w = HIST_WEIGHTINGS.get(weighting, weighting)
+    if not isinstance(w, (int, np.integer)):
+        raise IrtError(f"histogram: weighting {weighting!r} is none of {sorted(HIST_WEIGHTINGS)}", E_INVALID)
+    if band_edges is None:
+        return int(w), None, 1
+    e = np.ascontiguousarray(band_edges, dtype=np.float32).reshape(-1)
+    if e.size < 2:
+        raise IrtError(f"histogram: {e.size} band edges (at least 2)", E_INVALID)
+    return int(w), e, e.size - 1
+
+
+def histogram_cells(cells, value_range, bins: int, weighting="count", band_edges=None) -> dict:
+    """irt_histogram_cells, the histogram's definition on the host (no GPU): the (record, layer) items
+    of `cells` binned by value over value_range = (lower, upper) into `bins` bins, per altitude band
+    when band_edges (ascending radii, metres from the centre) is given; weighting "count" (1 per
+    item) or "thickness" (the layer's thickness in 1/64 m).  Returns uint64 arrays: bins (bands,
+    bins), tails (bands, 3: under, over, not finite) and outside (1: items in no band)."""
+    cells = np.ascontiguousarray(cells, dtype=CELL_DTYPE)
+    w, e, bands = _hist_args(weighting, band_edges)
+    out = {"bins": np.zeros((bands, max(int(bins), 0)), np.uint64), "tails": np.zeros((bands, 3), np.uint64),
+           "outside": np.zeros(1, np.uint64)}
+    _check(lib().irt_histogram_cells(_ptr(cells), cells.size, box1(*value_range), int(bins), w,
+                                     _ptr(e) if e is not None else None, bands,
+                                     HistogramOut(**{k: a.ctypes.data for k, a in out.items()})), "irt_histogram_cells")
     return out
 
 
@@ -1152,6 +1195,40 @@ class Context:
                 out.update({k: torch.empty((n,), dtype=tt[t], device=dev) for k, t in COLUMN_OUTPUTS.items()})
             self.section_raw(lat, lon, radius, {k: t.data_ptr() for k, t in out.items()}, weight, ambient, radiance,
                              mode, miss, torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
+    def histogram_raw(self, value_range, bins: int, out: dict, weighting="count", band_edges=None, stream: int = 0):
+        """irt_histogram: the histogram of the context's values (histogram_cells' definition) into the
+        device pointers of `out` -- any of bins (bands * bins uint64), tails (bands * 3) and outside
+        (1) --, overwritten, on `stream`.  Returns (bands, bins)."""
+        w, e, bands = _hist_args(weighting, band_edges)
+        unknown = set(out) - set(HISTOGRAM_OUTPUTS)
+        if unknown:
+            raise IrtError(f"histogram: unknown outputs {sorted(unknown)}", E_INVALID)
+        o = HistogramOut(**{k: int(v) or None for k, v in out.items()})
+        _check(lib().irt_histogram(self._h, box1(*value_range), int(bins), w, _ptr(e) if e is not None else None,
+                                   bands, o, C.c_void_p(stream)), "irt_histogram")
+        return bands, int(bins)
+
+    def histogram(self, value_range=None, bins: int = 300, weighting="count", band_edges=None, stream: int = 0) -> dict:
+        """The distribution of the field's values as the device holds them (every committed update
+        included): a dict of int64 torch tensors on the context's device -- bins (bands, bins), tails
+        (bands, 3: under, over, not finite), outside (1) -- holding the unsigned 64-bit counts of
+        histogram_cells.  value_range None: the context's dataRange.  With bins = the transfer
+        function's size, bin k is the LUT entry postClassify reads.  Enqueued on `stream`."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if value_range is None:
+            value_range = (self.info.dataRange.lower, self.info.dataRange.upper)
+        _, _, bands = _hist_args(weighting, band_edges)
+        with torch.cuda.device(dev):
+            out = {"bins": torch.empty((bands, max(int(bins), 0)), dtype=torch.int64, device=dev),
+                   "tails": torch.empty((bands, 3), dtype=torch.int64, device=dev),
+                   "outside": torch.empty((1,), dtype=torch.int64, device=dev)}
+            if stream == 0:  # the buffers were allocated on torch's current stream: stay behind it
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            self.histogram_raw(value_range, bins, {k: t.data_ptr() for k, t in out.items()}, weighting, band_edges,
+                               stream)
         return out
 
     def resample(self, points, mode: int = MODE_USER_GEOM, miss: float = float("nan")):

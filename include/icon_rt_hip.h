@@ -425,6 +425,61 @@ int irt_section_points(const float *lat, const float *lon, int numColumns,
 int irt_great_circle(float lat0, float lon0, float lat1, float lon1, int numPoints,
                      float *lat, float *lon, double *arc);
 
+/* ---------------------------------------------------------------- field statistics
+ * The distribution of the field's values, by value and by altitude band (a CFAD, contoured
+ * frequency by altitude diagram): what a caller chooses a transfer function or a value range from.
+ * After irt_update_values_device a step's values exist only on the device; this is the one pass
+ * over them.  The reference's transfer-function editor has the slot (common/alpha_editor.h:47-48,
+ * AlphaEditor::setHistogram) and never fills it.
+ *
+ * The definition (csrc/irt_histogram.h, compiled by the host helper and by the kernel).  Everything is
+ * float, every accumulator an unsigned 64-bit integer: the result does not depend on the order of the
+ * additions.  The items are every (record i, layer l) with 0 <= l < numLayers[i] over all records of
+ * the scene -- the values dataRange is folded from.  Per item, v = value[l], h0 = height[l], h1 =
+ * height[l+1]:
+ *  - Weight w.  IRT_HIST_COUNT: w = 1.  IRT_HIST_THICKNESS: d = h1 - h0; w = (uint64_t)(d * 64.0f),
+ *    truncating, when d > 0 and d <= 1048576.0f, else w = 0: the unit is 1/64 m (heights near 6.4e6 m
+ *    are multiples of 0.5 m, so nothing is lost).  ICON cells have nearly equal area, so thickness
+ *    stands in for volume.  An item with w == 0 is dropped entirely.
+ *  - Band b.  bandEdges == NULL: one band, every item in it.  Otherwise m = (h0 + h1) * 0.5f and the
+ *    item is in band b iff bandEdges[b] <= m && m < bandEdges[b+1]; an item in no band adds w to
+ *    outside[0] and goes nowhere else.
+ *  - Bin.  t = (v - lower) / (upper - lower), postClassify's normalisation (deviceCode.cu:129).  v not
+ *    finite, or t NaN: tails[3b + 2] += w.  Else t < 0: tails[3b + 0] += w.  Else t > 1: tails[3b + 1]
+ *    += w.  Else k = min((int)(t * (float)numBins), numBins - 1) and bins[b * numBins + k] += w.
+ *    With numBins == the transfer function's size, bin k is postClassify's LUT index clamp(idx, 0,
+ *    size - 1): the bins line up with the LUT entries.
+ * The sum of bins, tails and outside is the sum of w over the items. */
+#define IRT_HIST_COUNT 0
+#define IRT_HIST_THICKNESS 1
+typedef struct irt_histogram_out {   /* every pointer may be NULL: not written */
+  uint64_t *bins;     /* [numBands * numBins] */
+  uint64_t *tails;    /* [numBands * 3]: under, over, not finite */
+  uint64_t *outside;  /* [1] */
+} irt_histogram_out;
+/* The histogram of the context's records with the values of every committed update.  Equal to
+ * irt_histogram_cells on those records, integer for integer, however the context was made.
+ *  - d_out holds DEVICE pointers, used on `stream`; the call OVERWRITES them (it does not add to what
+ *    they held).  bandEdges is a HOST array of numBands + 1 floats, copied before the call returns;
+ *    when it is NULL, numBands must be 1.
+ *  - Ordering: a sampling call in the sense of "resampling" above -- no launch-ring slot, no render
+ *    statistics, IRT_E_CHAIN neither reported nor consumed; irt_update_values*, irt_set_transfunc and
+ *    irt_destroy wait for it; it runs after earlier sampling calls whatever their streams; between the
+ *    first irt_update_values* and irt_update_values_end it returns IRT_E_INVALID.  It takes no sampler
+ *    mode and needs neither a transfer function nor irt_build_wedge_accel.
+ *  - IRT_E_INVALID, nothing written: a NULL or still-building context, or a pending update; numBins
+ *    outside [1, 4096]; numBands outside [1, 64]; numBins * numBands > 4096; a valueRange that is not
+ *    finite or has upper <= lower; an unknown weighting; band edges that are not finite and strictly
+ *    ascending; NULL bandEdges with numBands != 1.
+ *  - A d_out of NULLs: IRT_OK, nothing launched.  A scene without records: IRT_OK, the outputs zeroed. */
+int irt_histogram(irt_context *ctx, irt_box1f valueRange, int numBins, int weighting,
+                  const float *bandEdges, int numBands, irt_histogram_out d_out, void *stream);
+/* Host helper and the definition, no GPU: the histogram of n records; out holds HOST pointers and is
+ * overwritten.  Refuses what irt_histogram refuses of these arguments, NULL cells with n > 0
+ * (IRT_E_INVALID) and a numLayers outside [0, 31] (IRT_E_DATA, as irt_create). */
+int irt_histogram_cells(const irt_icon_cell *cells, size_t n, irt_box1f valueRange, int numBins,
+                        int weighting, const float *bandEdges, int numBands, irt_histogram_out out);
+
 /* == clearFramebuffer (common/pipeline.cu:171-199): fb = make_rgba(0), accum = 0. */
 int irt_clear_frame(irt_context *ctx, uint32_t *d_fb, irt_vec4f *d_accum, size_t numPixels,
                     void *stream);
