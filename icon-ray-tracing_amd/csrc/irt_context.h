@@ -234,6 +234,9 @@ struct irt_context {
   size_t sampleTabCap = 0;          // floats in each
   hipEvent_t evSampleTab = nullptr;
   bool sampleTabBusy = false;
+  // Overlays (irt_overlay_create, irt_overlay.hip): the device objects this context owns, in the
+  // order of their creation; irt_overlay_destroy takes one out, free_overlays the rest
+  std::vector<irt_overlay *> overlays;
   // streaming creation (irt_create_begin / _append / _end): the cells and their glibc
   // corner trig go to HBM chunk by chunk; the volume facts, column count and sphere
   // records are folded on the host in record order
@@ -297,6 +300,8 @@ int tile_table(irt_context *c, const int32_t *ids, size_t n, int lo, int total, 
 // irt_sample.hip
 hipError_t wait_samples(irt_context *c);  // waits for every sampling call already issued
 void free_sample_state(irt_context *c);   // after wait_samples: its events, tables and staging
+// irt_overlay.hip
+void free_overlays(irt_context *c);       // after wait_samples: every overlay the context still owns
 
 namespace irt {
 // irt_launch.hip: what a frame's RenderArgs takes from the launch parameters, the transfer function

@@ -37,6 +37,15 @@
 //                                                thickness in 1/64 m; per altitude band between the
 //                                                ascending radii of --histogram-bands.  One line per
 //                                                band on stdout: the N counts, then the tails)
+//           [--graticule latStepDeg,lonStepDeg] [--lines FILE] [--line-width PX] [--lines-over]
+//                                               (lines on the globe, drawn into the frame the app writes,
+//                                                whichever render call made it: irt_render_overlay on the
+//                                                sphere of the shell's lower radius; one device.  FILE is
+//                                                text, one "lat lon" pair in degrees per line, a blank line
+//                                                between polylines, # starts a comment -- e.g. a coastline
+//                                                a user exports from Natural Earth; none is shipped.  Lines
+//                                                are PX pixels wide at the sub-camera point (default 1.5),
+//                                                under the volume or, --lines-over, on top of it)
 
 #include <math.h>
 #include <stdio.h>
@@ -45,6 +54,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <fstream>
 #include <string>
 #include <vector>
 
@@ -78,6 +88,11 @@ struct AppState {  // hostCode.cu:65-92 (the parts this backend uses)
   int histBins = 0;                  // --histogram: irt_histogram in place of the frame
   bool histogram = false, histThickness = false;
   std::vector<float> histBands;      // --histogram-bands: the band edges
+  std::vector<float> graticule;      // --graticule: latStepDeg, lonStepDeg
+  std::string linesFile;             // --lines
+  float lineWidth = 1.5f;            // --line-width, pixels
+  bool lineWidthGiven = false;
+  bool linesOver = false;            // --lines-over
 } g;
 
 void parseList(const std::string &list, std::vector<float> &out) {
@@ -139,7 +154,36 @@ void parseCommandLine(int argc, char *argv[]) {  // hostCode.cu:106-129
       g.histThickness = true;
     else if (arg == "--histogram-bands" && i + 1 < argc)
       parseList(argv[++i], g.histBands);
+    else if (arg == "--graticule" && i + 1 < argc)
+      parseList(argv[++i], g.graticule);
+    else if (arg == "--lines" && i + 1 < argc)
+      g.linesFile = argv[++i];
+    else if (arg == "--line-width" && i + 1 < argc)
+      g.lineWidth = strtof(argv[++i], nullptr), g.lineWidthGiven = true;
+    else if (arg == "--lines-over")
+      g.linesOver = true;
   }
+}
+
+// --lines FILE: "lat lon" in degrees per line, a blank line between polylines, # starts a comment
+bool readLines(const std::string &path, std::vector<float> &lat, std::vector<float> &lon, std::vector<int32_t> &first) {
+  std::ifstream f(path);
+  if (!f) return false;
+  const double rad = 3.14159265358979323846 / 180.0;
+  std::string line;  // of any length
+  first.assign(1, 0);
+  while (std::getline(f, line)) {
+    line = line.substr(0, line.find('#'));
+    double a, b;
+    if (sscanf(line.c_str(), "%lf %lf", &a, &b) == 2) {
+      lat.push_back((float)(a * rad));
+      lon.push_back((float)(b * rad));
+    } else if (first.back() != (int32_t)lat.size()) {
+      first.push_back((int32_t)lat.size());  // a blank line ends a polyline
+    }
+  }
+  if (first.back() != (int32_t)lat.size()) first.push_back((int32_t)lat.size());
+  return true;
 }
 
 void die(const char *what) {
@@ -184,6 +228,20 @@ int main(int argc, char *argv[]) {
     if (!g.histogram || g.histBins < 1 || g.histBands.size() == 1) {
       fprintf(stderr, "icon_rt: --histogram takes the number of bins (at least 1); --histogram-thickness and "
                       "--histogram-bands r0,r1,... (at least two radii) go with it\n");
+      return -1;
+    }
+  }
+
+  const bool lines = !g.graticule.empty() || !g.linesFile.empty();
+  if (lines || g.linesOver || g.lineWidthGiven) {
+    if (g.gpus > 0 || g.benchFrames > 0 || !g.section.empty() || g.histogram) {
+      fprintf(stderr, "icon_rt: --graticule and --lines draw into a frame on one device, without --bench, --section "
+                      "and --histogram\n");
+      return -1;
+    }
+    if (!lines || (!g.graticule.empty() && g.graticule.size() != 2) || !(g.lineWidth > 0.f)) {
+      fprintf(stderr, "icon_rt: --graticule takes latStepDeg,lonStepDeg; --line-width PX (positive) and --lines-over go "
+                      "with it or with --lines FILE\n");
       return -1;
     }
   }
@@ -348,6 +406,57 @@ int main(int argc, char *argv[]) {
     return 0;
   }
 
+  // the lines: segments of the graticule (style 1, thin and translucent) and of the file's polylines
+  // (style 0), PX pixels wide at the sub-camera point -- a pixel's angle at the frame's centre times
+  // the camera's distance from the sphere, over its radius
+  irt_overlay *overlay = nullptr;
+  irt_vec4f *cover = nullptr;
+  const float surface = info.sphericalBounds.lower.x;
+  if (lines) {
+    const double rad = 3.14159265358979323846 / 180.0;
+    float w = 0.f;
+    if (irt_overlay_width(&lp, surface, g.lineWidth, &w)) die("irt_overlay_width");
+    const irt_overlay_style styles[2] = {{{1.f, 1.f, 1.f, 1.f}, w}, {{0.75f, 0.75f, 0.75f, 0.7f}, w}};
+    std::vector<irt_overlay_segment> seg;
+    size_t nSeg = 0;
+    const float maxArc = (float)rad;  // 1 degree pieces
+    if (!g.linesFile.empty()) {
+      std::vector<float> lat, lon;
+      std::vector<int32_t> first;
+      if (!readLines(g.linesFile, lat, lon, first)) {
+        fprintf(stderr, "icon_rt: cannot read %s\n", g.linesFile.c_str());
+        return 1;
+      }
+      if (irt_overlay_segments(lat.data(), lon.data(), first.data(), (int)first.size() - 1, maxArc, 0, nullptr, 0, &nSeg))
+        die("irt_overlay_segments");
+      seg.resize(nSeg);
+      if (irt_overlay_segments(lat.data(), lon.data(), first.data(), (int)first.size() - 1, maxArc, 0, seg.data(),
+                               seg.size(), &nSeg))
+        die("irt_overlay_segments");
+    }
+    if (!g.graticule.empty()) {
+      const float sLat = (float)(g.graticule[0] * rad), sLon = (float)(g.graticule[1] * rad);
+      const size_t have = seg.size();
+      if (irt_graticule(sLat, sLon, maxArc, 1, nullptr, 0, &nSeg)) die("irt_graticule");
+      seg.resize(have + nSeg);
+      if (irt_graticule(sLat, sLon, maxArc, 1, seg.data() + have, nSeg, &nSeg)) die("irt_graticule");
+    }
+    if (irt_overlay_create(ctx, seg.data(), seg.size(), styles, 2, 0, &overlay)) die("irt_overlay_create");
+    // the line layer is lerped from the first frame on (0 * old at accumID 0): it starts cleared
+    const size_t coverBytes = (size_t)fb.width * fb.height * sizeof(irt_vec4f);
+    if (hipMalloc((void **)&cover, coverBytes) != hipSuccess || hipMemset(cover, 0, coverBytes) != hipSuccess) {
+      fprintf(stderr, "icon_rt: no device memory for the line layer (%zu bytes)\n", coverBytes);
+      return 1;
+    }
+    fprintf(stderr, "icon_rt: %zu line segments, half-width %.3g rad, %s the frame\n", seg.size(), (double)w,
+            g.linesOver ? "over" : "under");
+  }
+  auto drawLines = [&] {  // into the frame the render call just wrote
+    if (overlay && irt_render_overlay(ctx, overlay, &lp, fb.width, fb.height, surface, g.linesOver ? IRT_OVERLAY_OVER : 0,
+                                      fb.accumBuffer, cover, fb.fbPointer, nullptr, nullptr))
+      die("irt_render_overlay");
+  };
+
   pl.clearFramebuffer = [&] {
     if (irt_clear_frame(ctx, fb.fbPointer, fb.accumBuffer, (size_t)fb.width * fb.height, nullptr))
       die("clear");
@@ -362,12 +471,14 @@ int main(int argc, char *argv[]) {
                             g.levelsBack ? IRT_LEVELS_BACK : 0, fb.fbPointer, fb.accumBuffer, nullptr, nullptr, 0.f,
                             nullptr))
         die("irt_render_levels");
+      drawLines();
       return;
     }
     if (irt_render(ctx, &lp, fb.width, fb.height, fb.fbPointer, fb.accumBuffer, nullptr))
       die("irt_render");
     irt_render_stats st;
     irt_get_render_stats(ctx, &st);
+    drawLines();
   });
 
   do {  // hostCode.cu:931-965
@@ -416,9 +527,10 @@ int main(int argc, char *argv[]) {
     if (!f || fwrite(h.data(), 4, h.size(), f) != h.size()) die("dump-fb write");
     fclose(f);
   }
+  if (cover) (void)hipFree(cover);
   if (multi)
     irt_multi_destroy(multi);
   else
-    irt_destroy(ctx);
+    irt_destroy(ctx);  // (with its overlay)
   return 0;
 }

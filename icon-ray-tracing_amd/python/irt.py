@@ -146,6 +146,21 @@ HIST_WEIGHTINGS = {"count": HIST_COUNT, "thickness": HIST_THICKNESS}
 HIST_MAX_BINS, HIST_MAX_BANDS = 4096, 64
 
 
+class OverlayStyle(C.Structure):
+    """irt_overlay_style: a straight-alpha colour and a half-width in radians on the sphere."""
+    _fields_ = [("rgba", Vec4), ("halfWidth", C.c_float)]
+
+
+# irt_overlay_segment: 64 B
+SEGMENT_DTYPE = np.dtype([("a", "<f4", (3,)), ("b", "<f4", (3,)), ("n", "<f4", (3,)), ("t", "<f4", (3,)),
+                          ("sinHalf", "<f4"), ("style", "<i4"), ("pad", "<u4", (2,))])
+OVERLAY_MAX_STYLES = 8      # IRT_OVERLAY_MAX_STYLES
+OVERLAY_OVER = 1            # IRT_OVERLAY_OVER: the lines on top of the frame
+OVERLAY_MAX_HALF_WIDTH = 0.05
+OVERLAY_MAX_ARC = 0.2
+OVERLAY_MAX_BINS = 256
+
+
 def lib() -> C.CDLL:
     """Load the in-tree product library (fails loudly if it was not built)."""
     global _lib
@@ -193,6 +208,15 @@ def lib() -> C.CDLL:
             "irt_great_circle": [F, F, F, F, I, P, P, C.POINTER(C.c_double)],
             "irt_histogram": [P, Box1, I, I, P, I, HistogramOut, P],
             "irt_histogram_cells": [P, S, Box1, I, I, P, I, HistogramOut],
+            "irt_overlay_segments": [P, P, P, I, F, I, P, S, C.POINTER(S)],
+            "irt_graticule": [F, F, F, I, P, S, C.POINTER(S)],
+            "irt_overlay_bins": [P, S, F, I, P, P, S, C.POINTER(S)],
+            "irt_overlay_cover": [P, S, P, I, P, P, I, P, S, P],
+            "irt_overlay_create": [P, P, S, P, I, I, C.POINTER(P)],
+            "irt_overlay_destroy": [P, P],
+            "irt_overlay_get_bins": [P, P, C.POINTER(I), C.POINTER(S)],
+            "irt_overlay_width": [C.POINTER(LaunchParams), F, F, C.POINTER(F)],
+            "irt_render_overlay": [P, P, C.POINTER(LaunchParams), I, I, F, I, P, P, P, P, P],
             "irt_debug_sample_admits": [F, F, F],
             "irt_clear_frame": [P, P, P, S, P],
             "irt_render": [P, C.POINTER(LaunchParams), I, I, P, P, P],
@@ -348,6 +372,101 @@ def histogram_cells(cells, value_range, bins: int, weighting="count", band_edges
                                      _ptr(e) if e is not None else None, bands,
                                      HistogramOut(**{k: a.ctypes.data for k, a in out.items()})), "irt_histogram_cells")
     return out
+
+
+def _segments(seg) -> np.ndarray:
+    seg = np.ascontiguousarray(seg, dtype=SEGMENT_DTYPE).reshape(-1)
+    assert SEGMENT_DTYPE.itemsize == 64
+    return seg
+
+
+def overlay_styles(styles):
+    """Styles as the library takes them: a sequence of ((r, g, b, a), half_width) -- straight alpha, the
+    half-width in radians on the sphere -- as an array of OverlayStyle."""
+    styles = list(styles)
+    arr = (OverlayStyle * max(len(styles), 1))()
+    for k, (rgba, w) in enumerate(styles):
+        arr[k] = OverlayStyle(Vec4(*(float(x) for x in rgba)), float(w))
+    return arr, len(styles)
+
+
+def overlay_segments(lat, lon, first=None, max_arc: float = 0.0174533, style: int = 0) -> np.ndarray:
+    """irt_overlay_segments: polylines (lat, lon float32 radians; points first[l] .. first[l+1]-1 are
+    line l, None: one line) as great-circle segments no longer than max_arc, a SEGMENT_DTYPE array.
+    No GPU."""
+    lat = np.ascontiguousarray(lat, dtype=np.float32).reshape(-1)
+    lon = np.ascontiguousarray(lon, dtype=np.float32).reshape(-1)
+    if lat.size != lon.size:
+        raise IrtError(f"overlay_segments: {lat.size} lat for {lon.size} lon", E_INVALID)
+    first = np.ascontiguousarray([0, lat.size] if first is None else first, dtype=np.int32).reshape(-1)
+    if first.size < 1 or (first.size > 1 and int(first[-1]) > lat.size):
+        raise IrtError(f"overlay_segments: first ends at {first[-1] if first.size else None} of {lat.size} points",
+                       E_INVALID)
+    n = C.c_size_t()
+    args = (_ptr(lat), _ptr(lon), _ptr(first), first.size - 1, float(max_arc), int(style))
+    _check(lib().irt_overlay_segments(*args, None, 0, C.byref(n)), "irt_overlay_segments")
+    out = np.zeros(n.value, SEGMENT_DTYPE)
+    _check(lib().irt_overlay_segments(*args, _ptr(out), out.size, C.byref(n)), "irt_overlay_segments")
+    return out
+
+
+def graticule(step_lat: float, step_lon: float, max_arc: float = 0.0174533, style: int = 0) -> np.ndarray:
+    """irt_graticule: meridians every step_lon and parallels every step_lat (radians) as segments no
+    longer than max_arc (parallels: chains of great-circle arcs).  No GPU."""
+    n = C.c_size_t()
+    args = (float(step_lat), float(step_lon), float(max_arc), int(style))
+    _check(lib().irt_graticule(*args, None, 0, C.byref(n)), "irt_graticule")
+    out = np.zeros(n.value, SEGMENT_DTYPE)
+    _check(lib().irt_graticule(*args, _ptr(out), out.size, C.byref(n)), "irt_graticule")
+    return out
+
+
+def overlay_bins(segments, max_half_width: float, bins_per_edge: int):
+    """irt_overlay_bins: (binStart (6 N^2 + 1), binSeg), uint32 -- the cube-map bin table as CSR, each
+    bin's list ascending.  No GPU."""
+    seg = _segments(segments)
+    N = int(bins_per_edge)
+    if not 1 <= N <= OVERLAY_MAX_BINS:
+        raise IrtError(f"overlay_bins: binsPerEdge {N} is outside [1, {OVERLAY_MAX_BINS}]", E_INVALID)
+    start = np.zeros(6 * N * N + 1, np.uint32)
+    n = C.c_size_t()
+    _check(lib().irt_overlay_bins(_ptr(seg), seg.size, float(max_half_width), N, _ptr(start), None, 0, C.byref(n)),
+           "irt_overlay_bins")
+    lists = np.zeros(n.value, np.uint32)
+    _check(lib().irt_overlay_bins(_ptr(seg), seg.size, float(max_half_width), N, _ptr(start), _ptr(lists), lists.size,
+                                  C.byref(n)), "irt_overlay_bins")
+    return start, lists
+
+
+def overlay_cover(segments, styles, u, bins=None, bins_per_edge: int = 0) -> np.ndarray:
+    """irt_overlay_cover: the segment (lowest covering index, or -1) of every unit vector of u (..., 3)
+    float32, int32 of shape u.shape[:-1].  bins: None scans every segment; (binStart, binSeg) of
+    overlay_bins with its bins_per_edge scans each point's bin only.  No GPU."""
+    seg = _segments(segments)
+    st, ns = overlay_styles(styles)
+    u = np.ascontiguousarray(u, dtype=np.float32)
+    if u.ndim < 1 or u.shape[-1] != 3:
+        raise IrtError(f"overlay_cover: u of shape {u.shape} (..., 3)", E_INVALID)
+    out = np.full(u.shape[:-1], -2, np.int32)
+    start, lists = bins if bins is not None else (None, None)
+    _check(lib().irt_overlay_cover(_ptr(seg), seg.size, st, ns, _ptr(start) if start is not None else None,
+                                   _ptr(lists) if lists is not None else None, int(bins_per_edge), _ptr(u),
+                                   out.size, _ptr(out)), "irt_overlay_cover")
+    return out
+
+
+def overlay_width(lp: LaunchParams, height: int, surface_radius: float, pixels: float) -> float:
+    """irt_overlay_width: the half-width in radians on the sphere of surface_radius of a line `pixels`
+    pixels wide at the sub-camera point of lp's camera, for styles: a pixel's angle at the frame's centre
+    is |dir_dv| over dir_00's component along dir_du x dir_dv, its footprint that angle times the camera's
+    distance from the sphere, and the half-width half of `pixels` footprints over the radius -- clamped
+    to the legal range (1e-7, OVERLAY_MAX_HALF_WIDTH].  `height` (the frame dir_dv was made for) must be
+    positive and is otherwise not needed.  A convenience; no GPU."""
+    if int(height) < 1:
+        raise IrtError("overlay_width: height must be positive", E_INVALID)
+    w = C.c_float()
+    _check(lib().irt_overlay_width(C.byref(lp), float(surface_radius), float(pixels), C.byref(w)), "irt_overlay_width")
+    return float(w.value)
 
 
 def vec3(v) -> Vec3:
@@ -1231,6 +1350,32 @@ class Context:
                                stream)
         return out
 
+    def overlay(self, segments, styles, bins_per_edge: int = 0) -> "Overlay":
+        """irt_overlay_create: the segments (overlay_segments, graticule; concatenate for several
+        lines), their styles (overlay_styles' input) and the bin table on the device; bins_per_edge 0
+        lets the library choose.  Returns an Overlay: close() it, or leave it to the context."""
+        seg = _segments(segments)
+        st, ns = overlay_styles(styles)
+        h = C.c_void_p()
+        _check(lib().irt_overlay_create(self._h, _ptr(seg), seg.size, st, ns, int(bins_per_edge), C.byref(h)),
+               "irt_overlay_create")
+        return Overlay(self, h, seg.size)
+
+    def render_overlay(self, overlay: "Overlay", lp: LaunchParams, width: int, height: int, surface_radius: float,
+                       cover_ptr: int, fb_ptr: int, accum_in_ptr: int = 0, segment_ptr: int = 0, over: bool = False,
+                       stream: int = 0):
+        """irt_render_overlay: the overlay's lines on the sphere of surface_radius as lp's camera sees
+        it.  cover_ptr (float4 per pixel) holds the line layer, lerped with lp.accumID as a render
+        call lerps accum; it must hold finite values before the first frame (clear it: the lerp forms
+        0 * cover at accumID 0 too, and 0 * NaN is NaN for good); fb_ptr
+        takes the composite of the layer with accum_in_ptr (a frame's accum, read only; 0: none),
+        the lines under it or, over=True, on top; segment_ptr (int32; 0: not written) the segment
+        under each pixel, -1 for none.  Enqueued on `stream`."""
+        _check(lib().irt_render_overlay(self._h, overlay._h if overlay is not None else None, C.byref(lp), int(width),
+                                        int(height), float(surface_radius), OVERLAY_OVER if over else 0,
+                                        C.c_void_p(accum_in_ptr), C.c_void_p(cover_ptr), C.c_void_p(fb_ptr),
+                                        C.c_void_p(segment_ptr), C.c_void_p(stream)), "irt_render_overlay")
+
     def resample(self, points, mode: int = MODE_USER_GEOM, miss: float = float("nan")):
         """The field at `points` (..., 3): a float32 torch tensor on the context's device (sampled
         in place, on torch's current stream) or a numpy array (which goes up and comes back).
@@ -1280,6 +1425,32 @@ class Context:
         mo = np.zeros(n, dtype=np.float32)
         _check(lib().irt_get_shell(self._h, _ptr(vr), _ptr(mo)), "irt_get_shell")
         return vr, mo
+
+
+class Overlay:
+    """A device overlay of one Context (irt_overlay_create ... irt_overlay_destroy)."""
+
+    def __init__(self, ctx: Context, handle, num_segments: int):
+        self._ctx, self._h, self.num_segments = ctx, handle, int(num_segments)
+
+    def bins(self) -> tuple:
+        """irt_overlay_get_bins: (bins per edge, list entries) of the overlay's bin table."""
+        n, e = C.c_int(), C.c_size_t()
+        _check(lib().irt_overlay_get_bins(self._ctx._h, self._h, C.byref(n), C.byref(e)), "irt_overlay_get_bins")
+        return n.value, e.value
+
+    def close(self):
+        """irt_overlay_destroy (waits for the sampling calls issued so far); a context that was
+        closed first has freed it already."""
+        if self._h is not None and getattr(self._ctx, "_h", None):
+            _check(lib().irt_overlay_destroy(self._ctx._h, self._h), "irt_overlay_destroy")
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class DebugScene:

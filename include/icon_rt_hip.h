@@ -480,6 +480,129 @@ int irt_histogram(irt_context *ctx, irt_box1f valueRange, int numBins, int weigh
 int irt_histogram_cells(const irt_icon_cell *cells, size_t n, irt_box1f valueRange, int numBins,
                         int weighting, const float *bandEdges, int numBands, irt_histogram_out out);
 
+/* ---------------------------------------------------------------- overlay
+ * Lines on the globe -- coastlines, borders, a graticule -- drawn with the raygen's own jittered
+ * rays, so that they line up with a frame pixel for pixel and anti-alias with it over progressive
+ * frames.  An overlay is scene-independent: it reads a frame's accum and writes fb, so it composes
+ * with irt_render, irt_render_levels and irt_render_column.  No counterpart in the reference.
+ *
+ * The definition (csrc/irt_overlay.h, compiled by the host helpers and by the kernel; float, never an
+ * fma, with dot(x, y) = (x0*y0 + x1*y1) + x2*y2).  A line is a list of segments: arcs of great circles
+ * no longer than 0.2 rad, each drawn in one of up to IRT_OVERLAY_MAX_STYLES styles.  A style is a
+ * straight-alpha colour and a half-width W in radians on the sphere, 0 < W <= 0.05; from it, in double
+ * and rounded once to float, sinW = sin(W) and chord2 = (2 sin(W/2))^2.  A unit vector u is covered by
+ * segment i iff
+ *   body   = fabsf(dot(u,n)) <= sinW && fabsf(dot(u,t)) <= sinHalf && dot(u,a) + dot(u,b) > 0
+ *   cap(e) = with d = u - e per component, dot(d,d) <= chord2
+ *   covered = body || cap(a) || cap(b)
+ * with sinW and chord2 of the segment's style (the caps use chord lengths because cos W of a thin line
+ * rounds to 1.0f; the > 0 term keeps the antipodal arc out).  The segment of u is the LOWEST index that
+ * covers it, or -1.
+ * The bins: a cube map of N = binsPerEdge in [1, 256] bins per face edge, 6 N^2 bins.  The face of u
+ * is 2 * axis + (u[axis] < 0), axis that of the largest |component| (a tie goes to the lowest axis);
+ * (p, q) are the two other components, in axis order, each divided by |u[axis]|; i = min((int)((p +
+ * 1.f) * 0.5f * N), N - 1) clamped at 0, j likewise from q; bin = (face * N + j) * N + i. */
+#define IRT_OVERLAY_MAX_STYLES 8
+#define IRT_OVERLAY_OVER 1       /* irt_render_overlay: the lines on top of the frame */
+typedef struct irt_overlay_segment {   /* 64 B, one cache line */
+  float a[3], b[3];   /* the end points, unit vectors */
+  float n[3];         /* the unit normal of their great circle: a x b normalised */
+  float t[3];         /* the unit tangent at the arc's midpoint: b - a normalised */
+  float sinHalf;      /* the sine of half the arc */
+  int32_t style;
+  uint32_t pad[2];    /* zero */
+} irt_overlay_segment;
+typedef struct irt_overlay_style {
+  irt_vec4f rgba;     /* straight alpha */
+  float halfWidth;    /* radians on the sphere, in (0, 0.05] */
+} irt_overlay_style;
+typedef struct irt_overlay irt_overlay;
+
+/* Host helpers, no GPU.  Each refuses (IRT_E_INVALID, nothing written) NULL pointers with work to do,
+ * a style index outside its table, widths and arcs outside the ranges above, and 2^24 segments or more.
+ *
+ * irt_overlay_segments: polylines as segments.  lat, lon are float radians; points first[l] ..
+ * first[l+1]-1 are line l.  Unit vectors are computed in double on the axes of irt_latlon_points (x =
+ * cos lat cos lon, y = cos lat sin lon, z = sin lat), so a line at (lat, lon) lies over the field
+ * irt_sample_latlon reports there.  Consecutive points whose float unit vectors are equal are merged;
+ * every remaining leg is cut by slerp, in double, into ceil(arc / maxArc) equal pieces (0 < maxArc <=
+ * 0.2 rad), and every field of a piece is rounded to float at the end.  Also refused: a non-finite
+ * input, and consecutive antipodal points (irt_great_circle's rule).  *count = the segments needed;
+ * out == NULL only counts, capacity < *count is IRT_E_INVALID. */
+int irt_overlay_segments(const float *lat, const float *lon, const int32_t *first, int numLines,
+                         float maxArc, int style, irt_overlay_segment *out, size_t capacity,
+                         size_t *count);
+/* The graticule, built through irt_overlay_segments: the meridians lon = m stepLon, m = 0 ..
+ * floor(2 pi / stepLon) - 1, great-circle arcs pole to pole; the parallels lat = k stepLat for every
+ * integer k with |lat| < pi/2, closed chains of great-circle arcs of at most maxArc in longitude.  Such
+ * a chord of a parallel at latitude phi leaves the true parallel by (maxArc^2 / 8) sin phi cos phi at
+ * its middle: at 1 degree arcs at most 1.9e-5 rad, 121 m on the Earth, at 45 degrees (under 100 m
+ * poleward of 63 and equatorward of 27 degrees).  Steps in (0, pi] x (0, 2 pi] radians. */
+int irt_graticule(float stepLat, float stepLon, float maxArc, int style, irt_overlay_segment *out,
+                  size_t capacity, size_t *count);
+/* The bin table as CSR: binStart[6 N^2 + 1], and binSeg[binStart[b] .. binStart[b+1]) the segments of
+ * bin b, ASCENDING.  A segment goes to every bin whose bounding cap (its centre direction and the
+ * largest corner angle) comes within the sum of the radii plus 1e-5 rad of the segment's cap (the
+ * arc's midpoint, half the arc + maxHalfWidth), all in double: more bins than a segment covers points
+ * in, never fewer.  *count = the entries; binSeg == NULL fills binStart alone. */
+int irt_overlay_bins(const irt_overlay_segment *seg, size_t n, float maxHalfWidth, int binsPerEdge,
+                     uint32_t *binStart, uint32_t *binSeg, size_t capacity, size_t *count);
+/* The definition applied to numPoints unit vectors u[3 p ..]: segment[p] = the segment of point p.
+ * binStart == NULL scans every segment; else only the list of the point's bin, to its first hit. */
+int irt_overlay_cover(const irt_overlay_segment *seg, size_t n, const irt_overlay_style *styles,
+                      int numStyles, const uint32_t *binStart, const uint32_t *binSeg,
+                      int binsPerEdge, const float *u, size_t numPoints, int32_t *segment);
+
+/* A convenience: the half-width in radians on the sphere of surfaceRadius of a line `pixels` pixels wide
+ * at the sub-camera point of lp's camera.  In double, left to right: n = dir_du x dir_dv; focal =
+ * |dir_00 . n| / |n|; a pixel's angle at the frame's centre = |dir_dv| / focal; its footprint = that
+ * angle times | |org| - surfaceRadius |; *halfWidth = 0.5 * pixels * footprint / surfaceRadius, clamped to
+ * [1e-7, 0.05] and rounded to float.  IRT_E_INVALID: a NULL pointer, a surfaceRadius or pixels that is not
+ * finite and positive. */
+int irt_overlay_width(const irt_launch_params *lp, float surfaceRadius, float pixels, float *halfWidth);
+
+/* The device object: the segments, the styles and the bin table in memory the context owns (the
+ * segment array 64-byte aligned there).  binsPerEdge 0 picks N so that the mean list stays near 16
+ * entries, capped at 256.  n == 0 is legal: the render call then only composites.  A context may hold
+ * several overlays; irt_overlay_destroy waits for the sampling calls issued so far, and irt_destroy
+ * frees the overlays that are left. */
+int irt_overlay_create(irt_context *ctx, const irt_overlay_segment *seg, size_t n,
+                       const irt_overlay_style *styles, int numStyles, int binsPerEdge,
+                       irt_overlay **overlay);
+int irt_overlay_destroy(irt_context *ctx, irt_overlay *overlay);
+/* The bin table an overlay was created with: its bins per edge (the library's choice where 0 was asked
+ * for) and the number of list entries; either pointer may be NULL. */
+int irt_overlay_get_bins(const irt_context *ctx, const irt_overlay *overlay, int *binsPerEdge,
+                         size_t *numEntries);
+/* Draws the overlay into a frame of width x height pixels.  Per pixel p:
+ *  - the ray and the single hit slot of irt_render_column on the sphere of surfaceRadius: the near hit
+ *    when tn > 0, else the far hit when tf > 0; P = org + dir * t, len = sqrtf((P.x*P.x + P.y*P.y) +
+ *    P.z*P.z), u = P / len per component;
+ *  - s = the segment of u (through the bins), -1 for a pixel without a hit; d_segment[p] = s (d_segment
+ *    may be NULL): which line is under the cursor;
+ *  - the line sample L = (r*a, g*a, b*a, a) of s's style, or 0; d_cover[p] = w * L + (1 - w) *
+ *    d_cover[p] with w = 1 / (accumID + 1), the lerp of every render call: progressive frames
+ *    anti-alias the hard edge through the raygen's own jitter.  The product (1 - w) * d_cover[p] is
+ *    formed at accumID 0 too, where w = 1: d_cover must hold finite values before the first frame
+ *    (clear it, as irt_clear_frame clears accum) -- 0 * NaN and 0 * inf are NaN, and a NaN stays;
+ *  - with V = d_accum_in[p] (premultiplied, as every render call leaves it; 0 when d_accum_in is NULL)
+ *    and K = d_cover[p], one multiply and one add per component: out = V + (1 - V.w) * K (the lines
+ *    under the volume, on the Earth's surface), or with IRT_OVERLAY_OVER out = K + (1 - K.w) * V;
+ *  - d_fb[p] = make_rgba(linear_to_srgb(out.rgb), out.w), as every render call writes fb.
+ * d_accum_in is never written, so a progressive irt_render loop goes on undisturbed and its next frame
+ * rewrites fb from accum.  Every pixel of the frame is written.  Of lp the call uses the camera and
+ * accumID.  A sampling call in every respect of "resampling" above (the cell mode's checks: neither a
+ * transfer function nor irt_build_wedge_accel is needed): ordering, no launch-ring slot, no
+ * statistics, no IRT_E_CHAIN, refused while an update is pending.
+ * IRT_E_INVALID, nothing written: a NULL overlay, lp, d_cover or d_fb; an overlay of another context;
+ * a surfaceRadius that is not finite and positive; unknown flag bits; a frame irt_render_levels
+ * refuses.  Far-side lines seen through the globe, the tile forms, multi-GPU splitting and several
+ * frames per launch have no overlay form. */
+int irt_render_overlay(irt_context *ctx, const irt_overlay *overlay, const irt_launch_params *lp,
+                       int width, int height, float surfaceRadius, int flags,
+                       const irt_vec4f *d_accum_in, irt_vec4f *d_cover, uint32_t *d_fb,
+                       int32_t *d_segment, void *stream);
+
 /* == clearFramebuffer (common/pipeline.cu:171-199): fb = make_rgba(0), accum = 0. */
 int irt_clear_frame(irt_context *ctx, uint32_t *d_fb, irt_vec4f *d_accum, size_t numPixels,
                     void *stream);
