@@ -202,6 +202,7 @@ struct irt_context {
   long long voidOnDevice = 0;    // the cache generation d_voidList holds (0: none)
   bool voidOnDeviceList = false; // ... as the work-item list (else as the bitmap)
   long long lastVoid = 0;        // packets the last launch rendered as void (irt_debug_void_use)
+  long long lastInterior = 0;    // ... and flagged interior for its kernel (irt_debug_interior_use)
   long long lastWorkgroups = 0;  // the last launch's raygen grid (irt_debug_last_workgroups)
   irt::RenderPlan lastPlan{};    // ... and its kernel and grid as planned (irt_debug_last_plan)
   // persistent launches (RenderArgs::queue, IRT_QUEUE=0|1): every resident wave pulls 8x8

@@ -316,6 +316,7 @@ extern "C" int irt_debug_slot_use(const irt_context *c, double *tfSamples) {
 }
 
 extern "C" long long irt_debug_void_use(const irt_context *c) { return c ? c->lastVoid : -1; }
+extern "C" long long irt_debug_interior_use(const irt_context *c) { return c ? c->lastInterior : -1; }
 extern "C" long long irt_debug_last_workgroups(const irt_context *c) { return c ? c->lastWorkgroups : -1; }
 
 extern "C" int irt_debug_context_array(const irt_context *c, int which, void *dst, size_t capacity,

@@ -132,6 +132,28 @@ __device__ __forceinline__ void intersect_spheres(const Ray &r, float radiusA, f
   hitB = one(radiusB, nearB, farB);
 }
 
+// intersect_spheres for a ray of an interior packet (host/irt_void.cpp section 4: both discriminants
+// are >= 0 and recip_ok holds for A and both q): the same expressions in the same order on the
+// recip_d path alone -- no d < 0 exit, no guard, no fallback division -- so every bit is the same.
+__device__ __forceinline__ void intersect_spheres_interior(const Ray &r, float radiusA, float radiusB, float &nearA,
+                                                           float &farA, float &nearB, float &farB) {
+  const float A = dot3(r.dx, r.dy, r.dz, r.dx, r.dy, r.dz);
+  const float B = dot3(r.dx, r.dy, r.dz, r.ox, r.oy, r.oz) * 2.f;
+  const float OO = dot3(r.ox, r.oy, r.oz, r.ox, r.oy, r.oz);
+  const double rA = recip_d(A);
+  auto one = [&](float radius, float &tnear, float &tfar) {
+    const float C = OO - radius * radius;
+    const float d = sqrtf(B * B - 4.f * A * C);
+    const float q = B < 0.f ? -0.5f * (B - d) : -0.5f * (B + d);
+    const float t1 = div_recip(q, rA);
+    const float t2 = div_recip(C, recip_d(q));
+    tnear = fminf(t1, t2);
+    tfar = fmaxf(t1, t2);
+  };
+  one(radiusA, nearA, farA);
+  one(radiusB, nearB, farB);
+}
+
 // projectToSphericalGrid (ShellAccel.h:57-68), one axis: int((s-lo)/size*(dims-1))
 __device__ __forceinline__ int project_axis(float s, float lo, float hi, int dim) {
   return f2i_x86((s - lo) / (hi - lo) * (float)(dim - 1));

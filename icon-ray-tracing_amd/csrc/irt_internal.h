@@ -226,13 +226,19 @@ inline uint32_t void_row(uint32_t count, int F) {
   return (uint32_t)((((uint64_t)count + (uint64_t)F - 1) / (uint64_t)F + 7) & ~(uint64_t)7);
 }
 // bits: void_words(numTiles) words; returns the number of packets flagged.  lists (may be null): see above
-uint32_t void_packets(const VoidRequest &q, uint32_t *bits, VoidLists *lists = nullptr);
+// interior (may be null): void_words(numTiles) words, the packets every ray of which passes boxTest, hits
+// both spheres and takes the front-and-back ranges with every fast division's guard holding
+// (host/irt_void.cpp section 4), *numInterior their number; never one of the void packets
+uint32_t void_packets(const VoidRequest &q, uint32_t *bits, VoidLists *lists = nullptr, uint32_t *interior = nullptr,
+                      uint32_t *numInterior = nullptr);
 // ... and the last request's bitmap, kept while the request stays the same (tile lists by content)
 struct VoidCache {
   std::vector<unsigned char> key;
   std::vector<uint32_t> bits;
   VoidLists lists;                      // of the same request and generation as bits
   uint32_t count = 0;                   // packets flagged (0 while the bitmap is not computed)
+  std::vector<uint32_t> interior;       // the interior packets' bitmap, of the same request and generation
+  uint32_t interiorCount = 0;
   bool keyed = false, valid = false;    // a request was seen; its bitmap is computed
   long long generation = 0;             // bitmaps computed so far
   // true: computed anew.  defer: a new request is only noted, and computed when it comes again

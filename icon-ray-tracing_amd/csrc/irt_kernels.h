@@ -155,7 +155,17 @@ struct RenderArgs {
   const uint32_t *voidBits;
   const uint32_t *voidList;
   uint32_t voidLive, voidRow, voidCount;
+  // Interior packets of such a launch (host/irt_void.cpp section 4; 0: none flagged): every ray passes
+  // boxTest, hits both spheres and takes the front-and-back ranges, so the OPT_VOID kernels -- all
+  // four, within the registers, spills and LDS they had -- set the ray up
+  // without the box test, the range selection and the fallback divisions.  The list carries the class in the live item's top bit (kItemInterior); the
+  // bitmap form in a second bitmap behind the first, at voidBits + 2 numTiles.  (In the struct's tail
+  // padding: no other field moves, and the kernels without OPT_VOID are the parent's byte for byte.)
+  uint32_t interior;
 };
+// a live work item of an interior packet, as the device copy of the work-item list carries it (the
+// host's list, VoidLists::items, keeps plain packet numbers; ~0u stays the empty item)
+constexpr uint32_t kItemInterior = 1u << 31;
 // a persistent launch's queue words (irt_render.hip queue_take): 8 per-XCD counters and the
 // done count, each on its own 128-B line
 constexpr int kQueueLine = 32;

@@ -604,6 +604,7 @@ int setup_chain(irt_context *c, int numFrames, Launch &L) {
 int prepare_void(irt_context *c, const irt_launch_params *lp, const RenderRequest &r, Launch &L) {
   RenderArgs &A = L.A;
   c->lastVoid = 0;
+  c->lastInterior = 0;
   if (!(A.chain && !r.seq && r.numFrames > 1 && r.numFrames <= 65535 && L.numTiles > 0 &&
         c->chainWithhold < 0 && c->probeExit == 0 && !stats_variant(c) &&
         lp->raygen == IRT_RAYGEN_WITH_ACCEL && lp->accelMode == IRT_ACCEL_SPHERE &&
@@ -618,7 +619,9 @@ int prepare_void(irt_context *c, const irt_launch_params *lp, const RenderReques
   // bitmap on the plain grid (the terrain kernels always).
   const bool list = c->forms->voidList.fn != nullptr &&
                     (size_t)vl.live + void_row(vl.count, r.numFrames) < (size_t)L.numTiles * 64;
-  const size_t words = list ? vl.items.size() : void_words(L.numTiles);
+  // the interior class (the same request, computed in the same pass): the list's live items carry it
+  // in their top bit, the bitmap form as a second bitmap behind the first
+  const size_t words = list ? vl.items.size() : 2 * void_words(L.numTiles);
   if (words > c->voidCap) {
     // every launch that may still read the old words, on any stream, and every slot's staging
     int rc = grow(c, Retire::SlotsThenStream, L.s, &c->voidCap, words,
@@ -630,7 +633,16 @@ int prepare_void(irt_context *c, const irt_launch_params *lp, const RenderReques
   }
   if (c->voidOnDevice != c->voidCache.generation || c->voidOnDeviceList != list) {
     uint32_t *h = c->h_voidList + (size_t)L.slot * c->voidCap;
-    memcpy(h, list ? vl.items.data() : c->voidCache.bits.data(), words * sizeof(uint32_t));
+    if (list) {
+      const std::vector<uint32_t> &in = c->voidCache.interior;
+      for (size_t k = 0; k < words; ++k) {
+        const uint32_t p = vl.items[k];
+        h[k] = k < vl.live && p != kVoidEmpty && ((in[p >> 5] >> (p & 31)) & 1u) ? p | kItemInterior : p;
+      }
+    } else {
+      memcpy(h, c->voidCache.bits.data(), words / 2 * sizeof(uint32_t));
+      memcpy(h + words / 2, c->voidCache.interior.data(), words / 2 * sizeof(uint32_t));
+    }
     c->voidOnDeviceList = list;
     IRT_HIP(hipMemcpyAsync(c->d_voidList, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, L.s));
     c->voidOnDevice = c->voidCache.generation;
@@ -643,7 +655,9 @@ int prepare_void(irt_context *c, const irt_launch_params *lp, const RenderReques
   } else {
     A.voidBits = c->d_voidList;
   }
+  A.interior = c->voidCache.interiorCount;
   c->lastVoid = c->voidCache.count;
+  c->lastInterior = c->voidCache.interiorCount;
   return IRT_OK;
 }
 

@@ -576,7 +576,7 @@ __device__ __forceinline__ void render_pixel_coop(const RenderArgs &A, Tracer<OP
                                                   const float *s_th, int4 *s_dda, float4 *s_entry,
                                                   float4 *s_acc, CoopWave &W, ScanWave *SW, const uint2 *jmp,
                                                   int tid, int accumID, uint32_t blk, int pwave, int frame,
-                                                  int partSel = -1) {
+                                                  int partSel = -1, uint32_t interior = 0u) {
   // At 5+ waves/SIMD the pixel's output addresses are recomputed where they are used (from the
   // workgroup's uniform block index), not held in VGPRs through the rounds: a progressive
   // batch's sample slot (k_accumulate reads it) and the frame index.  (At 4 waves there is
@@ -634,6 +634,41 @@ __device__ __forceinline__ void render_pixel_coop(const RenderArgs &A, Tracer<OP
     gen_ray(A, accumID, px.x, px.y, st, dx, dy, dz, frame);
     const float3 O = cam_org(A, frame);
     const Ray ray = {O.x, O.y, O.z, 0.f, dx, dy, dz, 1e10f};
+    // Interior packets (host/irt_void.cpp section 4; the OPT_VOID kernels): every
+    // ray of the packet passes boxTest, hits both spheres and takes the front-and-back ranges, so
+    // the wave -- one scalar branch the compiler cannot see through -- skips the box test, the
+    // d < 0 exits, the range selection and the fallback divisions.  The ranges are those the
+    // general path below gives such a ray, bit for bit; both paths join before the state machine.
+    bool setUp = false;
+    if constexpr ((OPT & OPT_VOID) != 0) {
+      uint32_t iu = __builtin_amdgcn_readfirstlane(interior);
+      if constexpr ((OPT & OPT_VLIST) == 0) {
+        // the bitmap form: the packet's bit of the second bitmap, behind the first one's 2 numTiles words
+        const RenderArgs &BA = fresh_args();
+        const uint32_t pkt = (uint32_t)opaque_u((int)blk) * 4u + (uint32_t)opaque_u(pwave);
+        iu = BA.voidBits && BA.interior
+                 ? (scalar_word(BA.voidBits, 2u * (uint32_t)BA.numTiles + (pkt >> 5)) >> (pkt & 31u)) & 1u
+                 : 0u;
+        iu = __builtin_amdgcn_readfirstlane(iu);
+      }
+      asm volatile("" : "+s"(iu));
+      if (iu) {
+        setUp = true;
+        inBox = true;
+        phase = kRange;
+        if (!toSample && !chainLate && (OPT & OPT_LEAN) == 0)
+          __builtin_amdgcn_global_load_lds((const void *)(A.accum + px.outIdx),
+                                           (__attribute__((address_space(3))) void *)(s_acc + (tid & ~63)),
+                                           16, 0, kRecompute ? 2 : 0);
+        const RenderArgs &IA = fresh_args();
+        float st1, st2, st3, st4;
+        intersect_spheres_interior(ray, IA.sbHi.x, IA.sbLo.x, st1, st4, st2, st3);
+        rlo0 = st1; rhi0 = st2;
+        rlo1 = st3; rhi1 = st4;
+        numRanges = 2;
+      }
+    }
+    if (!setUp) {
     float t0, t1;
     const bool boxHit = box_test(ray, A, t0, t1);
 #ifdef IRT_PROBE_BUILD
@@ -682,6 +717,7 @@ __device__ __forceinline__ void render_pixel_coop(const RenderArgs &A, Tracer<OP
     } else if (toSample) {
       *sample_slot() = make_float4(0.f, 0.f, 0.f, kNoSample);  // deviceCode.cu:294-295
     }
+    }  // !setUp
   }
   const bool chainReady = !chainLate || __builtin_amdgcn_readfirstlane(chainSeen) == A.chainEpoch + (uint32_t)frame;
   if ((OPT & OPT_LEAN) == 0 && chainLate && chainReady && inBox)

@@ -120,6 +120,11 @@ __global__ void __launch_bounds__((OPT & OPT_WAVEWG) ? 64 : 256,
   constexpr bool kList = kVoid && (OPT & OPT_VLIST) != 0;
   static_assert(kVoid || (OPT & OPT_VLIST) == 0, "OPT_VLIST: a form of the OPT_VOID kernels");
   uint32_t vitem = 0u;  // kList: this workgroup's packet (4 block + wave)
+  // Interior packets (RenderArgs::interior; every OPT_VOID kernel): the
+  // packet's class by the scalar unit -- the live item's top bit, read here with the packet; the
+  // bitmap form reads the second bitmap's bit at the ray setup (nothing held through the prologue)
+  // -- for the ray setup's one scalar branch (render_pixel_coop)
+  uint32_t interior = 0u;
   static_assert(!kVoid || (wavewg && lean && Tracer<OPT>::kCoop &&
                            (OPT & (OPT_SPLIT | OPT_SLOT | OPT_STATS | OPT_TIMING | OPT_QUEUE | OPT_GRID | OPT_WEDGE)) == 0),
                 "void packets: the default kernels' plain grid form");
@@ -152,6 +157,9 @@ __global__ void __launch_bounds__((OPT & OPT_WAVEWG) ? 64 : 256,
       void_packet(VA, some ? vitem >> 2 : 0u, (int)(some ? vitem & 3u : 0u), some, some ? (uint32_t)VA.numSamples : 0u);
       return;
     }
+    // a live item: its class, then the plain packet number
+    interior = vitem >> 31;
+    vitem &= ~kItemInterior;
   }
   uint64_t tStart = 0;
   if constexpr ((OPT & OPT_TIMING) != 0) tStart = __builtin_amdgcn_s_memtime();
@@ -317,7 +325,7 @@ __global__ void __launch_bounds__((OPT & OPT_WAVEWG) ? 64 : 256,
         T.frame = frame;
         render_pixel_coop<OPT>(A, T, ppx, th_p, s_dda, s_entry, s_acc, s_coop[ltid >> 6],
                                &s_scan[Tracer<OPT>::kWaveScan ? ltid >> 6 : 0], s_jmp, ltid, cam_accum_id(A, frame),
-                               pblk, pw, frame, partSel);
+                               pblk, pw, frame, partSel, interior);
         if (A.chain && frame < A.numSamples - 1 && frame != A.chainWithhold) {
           // chained frames: this wave's pixels are written through; tell frame + 1's wave
 #ifdef IRT_PROBE_BUILD

@@ -241,6 +241,34 @@ int irt_debug_void_packets(irt_debug_void_cache *cache, const irt_launch_params 
   return IRT_OK;
 }
 
+int irt_debug_interior_packets(irt_debug_void_cache *cache, const irt_launch_params *lp, const irt_volume_info *info,
+                               int W, int H, int tileBegin, int tileStride, const int32_t *tileList, int listCount,
+                               uint32_t *bits, size_t capacity, uint32_t *numInterior, long long *computations) {
+  if (!lp || !info || !numInterior || W <= 0 || H <= 0 || tileBegin < 0 || tileStride <= 0 || listCount < 0) {
+    set_error("irt_debug_interior_packets: bad argument");
+    return IRT_E_INVALID;
+  }
+  const int total = ((W + 63) / 64) * ((H + 63) / 64);
+  const int numTiles = tileList ? listCount : tileBegin < total ? (total - tileBegin + tileStride - 1) / tileStride : 0;
+  for (int k = 0; tileList && k < listCount; ++k)
+    if (tileList[k] < 0 || tileList[k] >= total) {
+      set_error("irt_debug_interior_packets: tile id %d at %d outside [0, %d)", tileList[k], k, total);
+      return IRT_E_INVALID;
+    }
+  if (void_words(numTiles) > capacity || (!bits && capacity)) {
+    set_error("irt_debug_interior_packets: %zu words needed", void_words(numTiles));
+    return IRT_E_INVALID;
+  }
+  const VoidRequest q = void_request(*lp, *info, W, H, tileBegin, tileStride, numTiles, tileList);
+  VoidCache local;
+  VoidCache &vc = cache ? cache->c : local;
+  vc.lookup(q);
+  if (void_words(numTiles)) memcpy(bits, vc.interior.data(), void_words(numTiles) * sizeof(uint32_t));
+  *numInterior = vc.interiorCount;
+  if (computations) *computations = vc.generation;
+  return IRT_OK;
+}
+
 int irt_debug_void_lists(irt_debug_void_cache *cache, const irt_launch_params *lp, const irt_volume_info *info,
                          int W, int H, int tileBegin, int tileStride, const int32_t *tileList, int listCount,
                          int numFrames, uint32_t *items, size_t capacity, uint32_t *numLive, uint32_t *voidPerRow,

@@ -53,6 +53,50 @@
 //    2.1 u of exact, signs kept, so the float test passes when 2 c / D > 2.2 * 2.1 u * T / D; c >= 3e-7 T
 //    covers it.  Hence s = T (delta + 4e-7), and T < 1e9 keeps the ray's tmax = 1e10 out of it.
 //
+//
+// 4. Interior packets (the second bitmap): every ray of the packet's active pixels, whatever the
+//    jitter, passes boxTest, hits both spheres in front of the eye, takes the front-and-back case
+//    of the raygen's range selection (t0 < st2 and !(st4 < t0), t0 the float box entry, st2 the
+//    inner sphere's near hit, st4 the outer one's far hit) and keeps every divisor of
+//    intersect_spheres inside recip_ok's range.  k_render then leaves the box test, the d < 0 exits,
+//    the range selection and the fallback divisions out (irt_raygen.h).  For one rectangle, with
+//    tc, x0, delta and x = x0 + delta as in section 2 (sphere_rect) and r the inner radius:
+//    (a) the box: section 3, unchanged (in_box with the rectangle's delta).
+//    (b) the discriminant.  cl = cos(tc)(1 - x^2/2) - sin(tc) x <= cos(tc + x) must be positive
+//        (every tested ray points at the globe's side: B < 0); theta <= tc + x < 90 degrees then
+//        gives sin^2(theta) <= sm = 1 - cl^2.  The exact disc / (4 D^2)
+//        is then at least g = r^2 - P^2 sm, the float one is off by at most eps P^2 (section 2, the
+//        same operations with r for R), so it is >= 0 when g >= eps P^2; the certificate asks
+//        g >= 4 eps P^2, i.e. rho = eps P^2 / g <= 1/4.  The outer sphere: R >= r makes its float C no
+//        larger and its float disc no smaller (every operation monotone under rounding), so it hits
+//        whenever the inner one does -- the mirror of section 2's last paragraph.
+//    (c) the ranges.  With B < 0, q = -0.5 (B - d) = (|B| + d) / 2 has no cancellation.  Relative
+//        errors: |B| / 2 = D P cos(theta) by 3.1 u / cos(theta) <= 3.1 u / cl; d = sqrtf(disc) by rho
+//        (sqrt halves the disc's, the bound keeps it whole), and d <= 2 D R against |B| >= 2 D P cl,
+//        so q by eq = 3.1 u / cl + rho R / (P cl) + 2 u; C = O.O - r r by eC = 5.1 u P^2 / (P^2 - R^2)
+//        (the outer sphere's, the larger); a quotient through recip_d or the division by u.  Hence
+//        st2 = fminf(q / A, C / q) >= (1 - err) s / D and st4 >= q_R / A >= (1 - err) (the outer far
+//        root) >= (1 - err) s / D, with s the Euclidean distance to the inner sphere's near hit
+//        along the tested ray, D its length and err = eq + eC + 8 u.
+//        The box entry t0 = fmaxf(0, the three near slab quotients), each within 2.1 u of exact
+//        (section 3).  Per axis k: an eye inside the slab [lo_k, hi_k] has a near quotient <= 0.  An
+//        eye above it (o_k > hi_k; below: mirrored) and a ray pointing away: negative again.
+//        Pointing at it: the quotient is e_k / D, e_k = (o_k - hi_k) / |w_k| for the ray's unit
+//        direction w.  Where the slab's side clears the inner sphere, hi_k > r: the near hit X = O +
+//        s w has X_k <= r, so s |w_k| >= o_k - r and s >= e_k (1 + m_k), m_k = (hi_k - r) / (o_k -
+//        hi_k) -- for the very ray tested, no cone around it; t0 < st2 then follows from
+//        (1 + 3 u) < (1 + m_k)(1 - err).  Where it does not (a lat/lon-filtered grid's box need not
+//        contain the sphere), the rectangle's own bounds: |w_k| >= wk = min |c_k| / max |c| - delta
+//        over the four corner directions c (c_k is affine and |c| convex over the rectangle; all
+//        four c_k must point at the slab, or all away from it by more than delta |c|), and s >=
+//        s(cu) = P cu - sqrt(r^2 - P^2 (1 - cu^2)), decreasing in cos(theta) <= cu = min(1, cos(tc) +
+//        sin(tc) x): (o_k - hi_k) / wk (1 + 3 u) < (1 - err) s(cu).  D cancels throughout.
+//        !(st4 < t0) follows from t0 < (1 - err) s / D <= st4.
+//    (d) recip_ok: len = |d| before normalize is within 8 u M of [dmin, max |c|], both asked inside
+//        [1e-30, 1e30]; A = D^2 is within 3e-4 of 1; q lies in D P cl (1 - eq) .. D (P + R)(1 + eq),
+//        and P < 1e12, P cl > 1e-20 keep that inside 2^-100 .. 2^100 with room to spare.
+//    A packet the certificate does not cover is simply not interior: no quartering.  Tiles first.
+//
 // A camera any of this cannot cover (non-finite words, du/dv that let |d| vanish over a packet, a
 // box thinner than 2 s) classifies nothing.
 
@@ -137,10 +181,70 @@ bool sphere_clear(const View &v, const Rect &r, int depth) {
          sphere_clear(v, {r.a0, am, bm, r.b1}, depth + 1) && sphere_clear(v, {am, r.a1, bm, r.b1}, depth + 1);
 }
 
+// What section 4 needs of the scene, once per request
+struct Shell {
+  double P, r, R, eps;
+  double o[3], lo[3], hi[3];
+};
+// One rectangle against section 4 (b), (c), (d); delta: the rectangle's own, for the box test (a)
+bool interior_rect(const View &v, const Shell &g, const Rect &r, double &delta) {
+  const double u = ldexp(1.0, -24);
+  const double ha = 0.5 * (r.a1 - r.a0), hb = 0.5 * (r.b1 - r.b0);
+  const V3 c = v.dir(r.a0 + ha, r.b0 + hb);
+  const double lc = norm(c), h = sqrt(ha * ha * v.uu + hb * hb * v.vv + 2.0 * ha * hb * v.uv), dmin = lc - h;
+  if (!(lc > 0.0) || !(h < 0.16 * lc)) return false;
+  delta = 8.0 * u * (v.m0 + r.a1 * v.mu + r.b1 * v.mv) / dmin + 4e-5;
+  const double ct = dot(c, v.axis) / lc, x = 1.01 * h / dmin + delta + 1e-9;
+  if (!(ct > 0.0) || !(ct <= 1.0)) return false;
+  const double st = sqrt(std::max(0.0, 1.0 - ct * ct));
+  const double cl = ct * (1.0 - 0.5 * x * x) - st * x;  // <= cos(theta) of every tested ray
+  if (!(cl > 0.0)) return false;
+  // (b)
+  const double P2 = g.P * g.P, gg = g.r * g.r - P2 * (1.0 - cl * cl);
+  if (!(gg >= 4.0 * g.eps * P2)) return false;
+  const double rho = g.eps * P2 / gg;
+  // (c)
+  const double eq = 3.1 * u / cl + rho * g.R / (g.P * cl) + 2.0 * u;
+  const double eC = 5.1 * u * P2 / (P2 - g.R * g.R);
+  const double err = eq + eC + 8.0 * u;
+  if (!(err < 0.5)) return false;
+  const V3 cn[4] = {v.dir(r.a0, r.b0), v.dir(r.a1, r.b0), v.dir(r.a0, r.b1), v.dir(r.a1, r.b1)};
+  double cmax = 0.0;
+  for (const V3 &q : cn) cmax = std::max(cmax, norm(q));
+  const double cu = std::min(1.0, ct + st * x);
+  const double sLow = g.P * cu - sqrt(std::max(0.0, g.r * g.r - P2 * (1.0 - cu * cu)));  // <= s of every tested ray
+  for (int k = 0; k < 3; ++k) {
+    const bool above = g.o[k] > g.hi[k], below = g.o[k] < g.lo[k];
+    if (!above && !below) continue;  // inside the slab: a near quotient <= 0
+    const double gap = above ? g.o[k] - g.hi[k] : g.lo[k] - g.o[k];  // > 0
+    const double side = above ? g.hi[k] : -g.lo[k];                  // the slab's side towards the eye, from the centre
+    if (side > g.r) {
+      const double m = (side - g.r) / gap;
+      if ((1.0 + m) * (1.0 - err) > 1.0 + 4.0 * u) continue;
+    }
+    // the rectangle's own bounds
+    double kmin = INFINITY, kaway = INFINITY;
+    for (const V3 &q : cn) {
+      const double ck = k == 0 ? q.x : k == 1 ? q.y : q.z, toward = above ? -ck : ck;  // > 0: pointing at the slab
+      kmin = std::min(kmin, toward);
+      kaway = std::min(kaway, -toward);
+    }
+    if (kaway > delta * cmax * 1.0001 + 2e-5 * cmax) continue;  // every tested ray points away (the clamp: 2e-5)
+    const double wk = kmin / cmax - delta;
+    if (!(wk > 0.0) || !(gap / wk * (1.0 + 4.0 * u) < (1.0 - err) * sLow)) return false;
+  }
+  // (d)
+  if (!(dmin > 1e-30) || !(cmax < 1e30) || !(g.P < 1e12) || !(g.P * cl > 1e-20)) return false;
+  return true;
+}
+
 }  // namespace
 
-uint32_t void_packets(const VoidRequest &q, uint32_t *bits, VoidLists *lists) {
+uint32_t void_packets(const VoidRequest &q, uint32_t *bits, VoidLists *lists, uint32_t *interior,
+                      uint32_t *numInterior) {
   memset(bits, 0, void_words(q.numTiles) * sizeof(uint32_t));
+  if (interior) memset(interior, 0, void_words(q.numTiles) * sizeof(uint32_t));
+  if (numInterior) *numInterior = 0;
   if (lists) *lists = VoidLists();
   // only the raygen this certificate describes: woodcockTrackingWithAccel over the shell's spheres
   if (q.raygen != IRT_RAYGEN_WITH_ACCEL || q.accelMode != IRT_ACCEL_SPHERE || q.mode != IRT_MODE_USER_GEOM) return 0;
@@ -168,7 +272,10 @@ uint32_t void_packets(const VoidRequest &q, uint32_t *bits, VoidLists *lists) {
   const View v = {org, d00, du, dv, axis, dot(du, du), dot(dv, dv), fabs(dot(du, dv)), abs1(d00), abs1(du), abs1(dv),
                   cos(need), sin(need)};
   const int tilesX = (q.W + 63) / 64, total = tilesX * ((q.H + 63) / 64);
-  uint32_t count = 0;
+  // interior packets (section 4) need a real inner sphere
+  const bool wantInterior = interior != nullptr && r > 0.0;
+  const Shell shell = {P, r, R, eps, {org.x, org.y, org.z}, {q.bmin[0], q.bmin[1], q.bmin[2]}, {q.bmax[0], q.bmax[1], q.bmax[2]}};
+  uint32_t count = 0, countInterior = 0;
   // the work items, gathered in this pass: the live packets per residue of their block (mod 8), in
   // block then wave order, and the void ones
   std::vector<uint32_t> res[8], voids;
@@ -192,7 +299,10 @@ uint32_t void_packets(const VoidRequest &q, uint32_t *bits, VoidLists *lists) {
     double delta = 0.0;
     const Rect tile = {tx0 + 0.5, std::min(tx0 + 64, q.W) + 0.5, ty0 + 0.5, std::min(ty0 + 64, q.H) + 0.5};
     const int whole = sphere_rect(v, tile, delta);
-    if (whole == kAllHit && !lists) continue;
+    if (whole == kAllHit && !lists && !wantInterior) continue;
+    double tdelta = 0.0;
+    const bool tileInterior = wantInterior && (whole == kAllHit || whole == kCentreHits) &&
+                              interior_rect(v, shell, tile, tdelta) && in_box(tile.a0, tile.a1, tile.b0, tile.b1, tdelta);
     const bool tileVoid = whole == kClear && in_box(tile.a0, tile.a1, tile.b0, tile.b1, delta);
     for (int j = 0; j < 64; ++j) {
       const size_t p = (size_t)k * 64 + j;
@@ -200,7 +310,7 @@ uint32_t void_packets(const VoidRequest &q, uint32_t *bits, VoidLists *lists) {
       const int x0 = tx0 + (((sub & 3) << 4) | ((wave & 1) << 3)), y0 = ty0 + (((sub >> 2) << 4) | ((wave >> 1) << 3));
       if (x0 >= q.W || y0 >= q.H) continue;  // no active pixel: nothing to merge, and no work item
       bool isVoid = tileVoid;
-      if (!tileVoid && whole != kAllHit) {
+      if (!tileVoid && whole != kAllHit && !tileInterior) {
         // one past the last active pixel
         const Rect r = {x0 + 0.5, std::min(x0 + 8, q.W) + 0.5, y0 + 0.5, std::min(y0 + 8, q.H) + 0.5};
         double pd = 0.0;  // (pd: the packet's own delta, for the box)
@@ -208,6 +318,16 @@ uint32_t void_packets(const VoidRequest &q, uint32_t *bits, VoidLists *lists) {
       }
       if (!isVoid) {
         if (lists) res[(p >> 2) & 7].push_back((uint32_t)p);
+        bool isInterior = tileInterior;
+        if (wantInterior && !tileInterior && !tileVoid) {
+          const Rect r = {x0 + 0.5, std::min(x0 + 8, q.W) + 0.5, y0 + 0.5, std::min(y0 + 8, q.H) + 0.5};
+          double pd = 0.0;
+          isInterior = interior_rect(v, shell, r, pd) && in_box(r.a0, r.a1, r.b0, r.b1, pd);
+        }
+        if (isInterior) {
+          interior[p >> 5] |= 1u << (p & 31);
+          ++countInterior;
+        }
         continue;
       }
       bits[p >> 5] |= 1u << (p & 31);
@@ -226,6 +346,7 @@ uint32_t void_packets(const VoidRequest &q, uint32_t *bits, VoidLists *lists) {
       for (size_t k = 0; k < res[x].size(); ++k) lists->items[8 * k + x] = res[x][k];
     std::copy(voids.begin(), voids.end(), lists->items.begin() + 8 * len);
   }
+  if (numInterior) *numInterior = countInterior;
   return count;
 }
 
@@ -246,10 +367,12 @@ bool VoidCache::lookup(const VoidRequest &q, bool defer) {
     keyed = true;
     valid = false;
     count = 0;
+    interiorCount = 0;
     if (defer) return false;
   }
   bits.assign(void_words(q.numTiles), 0u);
-  count = void_packets(q, bits.data(), &lists);
+  interior.assign(void_words(q.numTiles), 0u);
+  count = void_packets(q, bits.data(), &lists, interior.data(), &interiorCount);
   valid = true;
   ++generation;
   return true;

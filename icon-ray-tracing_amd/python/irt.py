@@ -485,9 +485,9 @@ def default_kernel_id(ctx=None) -> int:
     where the launches use the slot table (irt_debug_slot_use) -- or, without a context,
     that of the default variant.
 
-    A restatement of the library's launch plan kept for the profile lookups keyed on it, not a
-    read of it: after a launch that ran the void work-item list it says | 16 where the kernel was
-    the | 16 | 64 one.  Context.last_plan() gives the kernel the last launch in fact ran."""
+    A restatement of the library's launch plan kept for the profile lookups keyed on it; after a
+    launch that carried void data it takes the list bit (| 64) from Context.last_plan(), so the
+    lookup names the kernel the launch in fact ran (the flat kernel's work-item list form)."""
     L = lib()
     if ctx is not None:
         L.irt_debug_get_variant.argtypes = [C.c_void_p]
@@ -498,6 +498,7 @@ def default_kernel_id(ctx=None) -> int:
             v |= 128  # VariantForms::slot: the default kernels' OPT_SLOT form
         elif ctx.void_use() > 0:
             v |= 16  # ... their OPT_VOID form: the last launch carried a void-packet bitmap
+            v |= ctx.last_plan()[0] & 64  # ... or the work-item list (OPT_VLIST)
         return v
     return int(L.irt_debug_default_variant()) & ~4096  # OPT_MONO: one kernel per frame
 
@@ -783,6 +784,32 @@ def void_packets(lp: LaunchParams, info: VolumeInfo, w: int, h: int, tile_begin:
     return out
 
 
+def interior_packets(lp: LaunchParams, info: VolumeInfo, w: int, h: int, tile_begin: int = 0,
+                     tile_stride: int = 1, tiles=None, cache: VoidCache = None) -> np.ndarray:
+    """irt_debug_interior_packets: bool per packet of the launch, numbered as void_packets numbers them:
+    every ray of the packet, whatever the jitter, passes boxTest, hits both spheres and takes the
+    front-and-back ranges with the fast divisions' guards holding."""
+    L = lib()
+    L.irt_debug_interior_packets.argtypes = [C.c_void_p, C.POINTER(LaunchParams), C.POINTER(VolumeInfo), C.c_int,
+                                             C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_longlong)]
+    total = num_tiles(w, h)
+    t = None if tiles is None else np.ascontiguousarray(tiles, dtype=np.int32)
+    nt = len(t) if t is not None else (max(0, (total - tile_begin + tile_stride - 1) // tile_stride)
+                                       if tile_begin < total else 0)
+    bits = np.zeros(max(2 * nt, 1), np.uint32)
+    n, comp = C.c_uint32(), C.c_longlong()
+    _check(L.irt_debug_interior_packets(cache._h if cache else None, C.byref(lp), C.byref(info), w, h, tile_begin,
+                                        tile_stride, _ptr(t) if t is not None else None, nt if t is not None else 0,
+                                        _ptr(bits), bits.size, C.byref(n), C.byref(comp)),
+           "irt_debug_interior_packets")
+    if cache:
+        cache.computations = comp.value
+    out = ((bits[:2 * nt, None] >> np.arange(32, dtype=np.uint32)[None, :]) & 1).astype(bool).reshape(-1)
+    assert int(out.sum()) == n.value
+    return out
+
+
 def void_lists(lp: LaunchParams, info: VolumeInfo, w: int, h: int, frames: int, tile_begin: int = 0,
                tile_stride: int = 1, tiles=None, cache: VoidCache = None):
     """irt_debug_void_lists: the work items of a chained launch of `frames` frames that renders its void
@@ -1053,6 +1080,17 @@ class Context:
         L.irt_debug_void_use.argtypes = [C.c_void_p]
         L.irt_debug_void_use.restype = C.c_longlong
         return L.irt_debug_void_use(self._h)
+
+    def interior_use(self) -> int:
+        """Packets the last launch flagged interior for its kernel (the host's count of the class it
+        uploaded: such packets' rays are set up with no box test and no range guards); 0: no void
+        data, or no such packet."""
+        L = lib()
+        if not hasattr(L, "irt_debug_interior_use"):  # an older build loaded through IRT_LIB_PATH (A/B tools)
+            return 0
+        L.irt_debug_interior_use.argtypes = [C.c_void_p]
+        L.irt_debug_interior_use.restype = C.c_longlong
+        return L.irt_debug_interior_use(self._h)
 
     def last_workgroups(self) -> int:
         """Workgroups the last launch dispatched for its raygen (grid x * grid y)."""

@@ -235,6 +235,19 @@ int irt_debug_void_packets(irt_debug_void_cache *cache, const irt_launch_params 
  * single frame, a sequence of views, unchained frames, the chain test hook set, a statistics or
  * persistent variant, or no packet qualified); -1 for NULL. */
 long long irt_debug_void_use(const irt_context *ctx);
+/* Interior packets of the same request (arguments, cache and bit numbering as irt_debug_void_packets;
+ * computed in the same pass, so a cache's *computations counts both): the packets all of whose rays,
+ * whatever the jitter, pass boxTest, hit both of the shell's spheres in front of the eye and take the
+ * raygen's front-and-back ranges with every fast division's guard holding (host/irt_void.cpp section
+ * 4) -- the packets a launch that renders void packets sets up without the box test and the range
+ * guards.  Never a void packet.  *numInterior: bits set. */
+int irt_debug_interior_packets(irt_debug_void_cache *cache, const irt_launch_params *lp, const irt_volume_info *info,
+                               int W, int H, int tileBegin, int tileStride, const int32_t *tileList, int listCount,
+                               uint32_t *bits, size_t capacity, uint32_t *numInterior, long long *computations);
+/* Packets the context's last launch flagged interior for its kernel -- the host's count of the class it
+ * uploaded with the launch's void data, not a count taken on the device (0: the launch carried no void
+ * data -- see irt_debug_void_use --, or no packet qualified); -1 for NULL. */
+long long irt_debug_interior_use(const irt_context *ctx);
 /* The work items of such a launch of numFrames frames (no context, no device; request and cache as
  * irt_debug_void_packets): a launch that renders void packets runs a grid of numFrames rows of
  * *numLive + *voidPerRow one-wave workgroups, each reading its packet (4 * block + wave) from a list.
