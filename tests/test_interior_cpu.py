@@ -17,6 +17,7 @@ import pytest
 
 import irt
 import oracle as O
+from classifier_cameras import WINDOW_EYE, _box32, _lcg_jitters, _packet_rects, _rays32, _recip_ok, _sphere32
 from helpers import FRAMING
 
 F = np.float32
@@ -38,69 +39,6 @@ def _info(filtered=False):
         c = c[(c["lat"].min(1) > 0.2) & (c["lat"].max(1) < 1.0) & (c["lon"].min(1) > -0.5) & (c["lon"].max(1) < 0.6)]
         assert len(c) > 0
     return irt.volume_info(np.ascontiguousarray(c))
-
-
-def _packet_rects(W, H):
-    tx, ty = (W + 63) // 64, (H + 63) // 64
-    p = np.arange(tx * ty * 64)
-    blk, wave = p >> 2, p & 3
-    k, sub = blk >> 4, blk & 15
-    x0 = (k % tx) * 64 + ((sub & 3) << 4) + ((wave & 1) << 3)
-    y0 = (k // tx) * 64 + ((sub >> 2) << 4) + ((wave >> 1) << 3)
-    return x0, y0, np.minimum(x0 + 8, W), np.minimum(y0 + 8, H)
-
-
-def _dot(a, b):  # vecmath.h:536-538 order
-    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
-
-
-def _rays32(cam, xs, ys, ju, jv):
-    """generateRay in float32: (raw length, clamped unit direction)."""
-    d00, du, dv = cam[3:6], cam[6:9], cam[9:12]
-    a = (xs.astype(F) + F(0.5)) + ju.astype(F)
-    b = (ys.astype(F) + F(0.5)) + jv.astype(F)
-    d = np.stack([(d00[k] + a * du[k]) + b * dv[k] for k in range(3)], -1)
-    ln = np.sqrt(_dot(d, d))
-    d = d / ln[..., None]
-    d = np.where(np.abs(d) < F(1e-5), F(1e-5), d)
-    assert d.dtype == F
-    return ln, d
-
-
-def _box32(org, d, lo, hi):
-    tl, th = (lo - org) / d, (hi - org) / d
-    nr, fr = np.minimum(tl, th), np.maximum(tl, th)
-    t0 = np.maximum(F(0), np.maximum(np.maximum(nr[..., 0], nr[..., 1]), nr[..., 2]))
-    t1 = np.minimum(F(1e10), np.minimum(np.minimum(fr[..., 0], fr[..., 1]), fr[..., 2]))
-    return t0 < t1, t0, t1
-
-
-def _sphere32(org, d, radius):
-    """intersectSphere: (disc, A, q, tnear, tfar); q and the roots are NaN where disc < 0."""
-    A = _dot(d, d)
-    B = _dot(d, np.broadcast_to(org, d.shape)) * F(2)
-    Cc = _dot(org, org) - F(radius) * F(radius)
-    disc = B * B - F(4) * A * Cc
-    with np.errstate(invalid="ignore", divide="ignore"):
-        s = np.sqrt(disc)
-        q = np.where(B < 0, F(-0.5) * (B - s), F(-0.5) * (B + s))
-        t1, t2 = q / A, Cc / q
-    return disc, A, q, np.minimum(t1, t2), np.maximum(t1, t2)
-
-
-def _recip_ok(v):
-    a = np.abs(v)
-    return (a >= F(2.0 ** -100)) & (a <= F(2.0 ** 100))
-
-
-def _lcg_jitters(aid, W, H, xs, ys):
-    L = O.olib()
-    two = np.zeros(2, F)
-    ju, jv = np.zeros(xs.shape, F), np.zeros(xs.shape, F)
-    for i, (x, y) in enumerate(zip(xs.ravel(), ys.ravel())):
-        L.oracle_lcg((aid * W * H + int(x)) & 0xFFFFFFFF, int(y), 2, two.ctypes.data)
-        jv.ravel()[i], ju.ravel()[i] = two  # the dir_dv jitter is drawn first
-    return ju, jv
 
 
 def _check_packets(lp, info, W, H, flagged):
@@ -148,7 +86,6 @@ def _check_packets(lp, info, W, H, flagged):
 
 
 OFF_AXIS = ((1.0e7, 4.0e6, 9.0e6), (3.0e6, 2.0e6, 0.0), (0.0, 1.0, 0.0), 40.0)
-WINDOW_EYE = ((1.2e7, 1.0e6, 9.0e6), (4.6e6, 2.0e5, 3.6e6), (0.0, 0.0, 1.0), 35.0)
 CAMERAS = [
     ("framing 64x64", FRAMING, 64, 64, False, True),
     ("framing 96x72", FRAMING, 96, 72, False, True),
