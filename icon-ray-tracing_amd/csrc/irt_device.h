@@ -39,18 +39,29 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
   return ax * bx + ay * by + az * bz;  // vecmath.h:536-538 order
 }
 
-// Correctly rounded a / b for per-lane divisors through a double reciprocal, cheaper than the
-// f32 division sequence (v_div_scale x2, v_rcp, five fmas, v_div_fmas, v_div_fixup) when
+// a / b as the f32 division rounds it, for per-lane divisors through a double reciprocal, cheaper
+// than the f32 division sequence (v_div_scale x2, v_rcp, five fmas, v_div_fmas, v_div_fixup) when
 // one divisor serves several quotients.  r = the hardware estimate of 1/b (v_rcp_f32, within
 // 1 ulp: |e| <= 2^-22 for e = 1 - b r) refined once cubically, r (1 + e + e^2), by double
 // fmas: relative error e^3 plus three roundings, below 2^-52.  Then (double)a * r is within
 // 2^-51 (relative) of a/b, while a quotient of two floats that is not itself representable
-// lies at least 2^-49 from every rounding boundary of the float grid (a - b m, for a boundary
+// lies at least 2^-49 from every rounding boundary of the NORMAL float grid (a - b m, for a boundary
 // m, is a nonzero multiple of 2^min(ea, eb+em): the same argument as div_uniform), so the
-// double product rounds to the float a / b rounds to -- overflow to inf and float subnormal
-// results included.  Valid for 2^-100 <= |b| <= 2^100 (no zero, inf, NaN or subnormal
+// double product (div_product) rounds to the float a / b rounds to, overflow to inf included.
+// Not so below FLT_MIN: a midpoint between two subnormal floats has fewer than 25 significant bits,
+// a quotient of two floats can be exactly one (147 2^-149 / 98 = 1.5 2^-149), a / b then rounds it
+// to even and the product, off by the reciprocal's rounding, to either side.  So a product that
+// comes out subnormal (div_unsettled: one v_cmp_class) is redone by the division itself, in
+// div_recip / div_uniform or by the caller for several quotients at once.  A zero product is final
+// (a quotient that is no tie lies 2^-48 or more, relative, from the tie 2^-150, so the product is on
+// the division's side of it, and on the tie itself only a product above it differs: it is
+// subnormal); so is FLT_MIN (the boundary below it, (2^24 - 1) 2^-150, has 24 bits: a quotient of
+// floats reaches it only with a power-of-two divisor, whose reciprocal is exact).
+// Valid for 2^-100 <= |b| <= 2^100 (no zero, inf, NaN or subnormal
 // divisor, no double overflow); recip_ok(b) tests that and callers divide otherwise.
-// tests/test_host_logic.py checks the identity with estimates perturbed by up to 2 ulps.
+// tests/test_host_logic.py checks the identity with estimates perturbed by up to 2 ulps, on the
+// exact subnormal ties and on quotients 2^-48 from a normal-range midpoint too; tests/
+// test_gpu_raymath.py runs both forms on the device.
 __device__ __forceinline__ bool recip_ok(float b) {
   const float ab = __builtin_fabsf(b);
   return ab >= 0x1p-100f && ab <= 0x1p100f;
@@ -60,20 +71,43 @@ __device__ __forceinline__ double recip_d(float b) {
   const double e = __builtin_fma(-(double)b, r0, 1.0);
   return __builtin_fma(r0, __builtin_fma(e, e, e), r0);
 }
-__device__ __forceinline__ float div_recip(float a, double r) { return (float)((double)a * r); }
+__device__ __forceinline__ float div_product(float a, double r) { return (float)((double)a * r); }
+// a product that is a subnormal float (either sign): the one kind the division may round otherwise
+__device__ __forceinline__ bool div_unsettled(float f) { return __builtin_amdgcn_classf(f, 0x90); }
+__device__ __forceinline__ float div_recip(float a, float b, double r) {
+  const float f = div_product(a, r);
+  if (__builtin_expect(div_unsettled(f), 0)) return a / b;
+  return f;
+}
 
-// boxTest (vecmath.h:1926-1937); the six quotients through one reciprocal per axis
+// The reference's fminf / fmaxf on its CPU (vecmath.h:504-533; x86-64 glibc: minss / maxss after a
+// NaN test): of two equal operands the SECOND -- which matters for +0 against -0 only, where
+// v_min_f32 / v_max_f32 order -0 below +0 whichever comes first.  NaN operands as fminf / fmaxf.
+__device__ __forceinline__ float min_ref(float x, float y) { return x == y ? y : fminf(x, y); }
+__device__ __forceinline__ float max_ref(float x, float y) { return x == y ? y : fmaxf(x, y); }
+
+// boxTest (vecmath.h:1926-1937); the six quotients through one reciprocal per axis, all six by the
+// division when a divisor is outside recip_ok or a product comes out subnormal.  A slab quotient is
+// a zero when the eye lies in a face's plane (or the direction component is infinite), and two
+// zeros of opposite sign can meet in the reductions (tests/test_gpu_raymath.py found the plain
+// minimum's +0 for the reference's -0).  Which zero a reduction picks changes nothing unless that
+// zero is the result, so t0 and t1 come from the plain minima and maxima, and only a t0 or t1 that
+// is a zero (an eye inside the box or in a face's plane) is reduced again by the reference's rule.
 __device__ __forceinline__ bool box_test(const Ray &r, const RenderArgs &A, float &t0, float &t1) {
   float lx, ly, lz, hx, hy, hz;
-  if (recip_ok(r.dx) && recip_ok(r.dy) && recip_ok(r.dz)) {
+  bool fast = recip_ok(r.dx) && recip_ok(r.dy) && recip_ok(r.dz);
+  if (fast) {
     const double rx = recip_d(r.dx), ry = recip_d(r.dy), rz = recip_d(r.dz);
-    lx = div_recip(A.bmin.x - r.ox, rx);
-    ly = div_recip(A.bmin.y - r.oy, ry);
-    lz = div_recip(A.bmin.z - r.oz, rz);
-    hx = div_recip(A.bmax.x - r.ox, rx);
-    hy = div_recip(A.bmax.y - r.oy, ry);
-    hz = div_recip(A.bmax.z - r.oz, rz);
-  } else {
+    lx = div_product(A.bmin.x - r.ox, rx);
+    ly = div_product(A.bmin.y - r.oy, ry);
+    lz = div_product(A.bmin.z - r.oz, rz);
+    hx = div_product(A.bmax.x - r.ox, rx);
+    hy = div_product(A.bmax.y - r.oy, ry);
+    hz = div_product(A.bmax.z - r.oz, rz);
+    fast = ((int)div_unsettled(lx) | (int)div_unsettled(ly) | (int)div_unsettled(lz) | (int)div_unsettled(hx) |
+            (int)div_unsettled(hy) | (int)div_unsettled(hz)) == 0;
+  }
+  if (__builtin_expect(!fast, 0)) {
     lx = (A.bmin.x - r.ox) / r.dx, ly = (A.bmin.y - r.oy) / r.dy, lz = (A.bmin.z - r.oz) / r.dz;
     hx = (A.bmax.x - r.ox) / r.dx, hy = (A.bmax.y - r.oy) / r.dy, hz = (A.bmax.z - r.oz) / r.dz;
   }
@@ -81,6 +115,10 @@ __device__ __forceinline__ bool box_test(const Ray &r, const RenderArgs &A, floa
   const float fx = fmaxf(lx, hx), fy = fmaxf(ly, hy), fz = fmaxf(lz, hz);
   t0 = fmaxf(r.tmin, fmaxf(fmaxf(nx, ny), nz));
   t1 = fminf(r.tmax, fminf(fminf(fx, fy), fz));
+  if (__builtin_expect(t0 == 0.f || t1 == 0.f, 0)) {
+    t0 = max_ref(r.tmin, max_ref(max_ref(min_ref(lx, hx), min_ref(ly, hy)), min_ref(lz, hz)));
+    t1 = min_ref(r.tmax, min_ref(min_ref(max_ref(lx, hx), max_ref(ly, hy)), max_ref(lz, hz)));
+  }
   return t0 < t1;
 }
 
@@ -101,7 +139,7 @@ __device__ __forceinline__ bool intersect_sphere(const Ray &r, float radius, flo
 }
 // The raygen's two intersectSphere calls on one ray (the shell's outer and inner sphere,
 // ShellAccel.h:94-95): the same expressions, A = dot(dir, dir) shared, each quotient through
-// recip_d when its divisor allows.
+// recip_d when its divisor allows and neither product comes out subnormal.
 __device__ __forceinline__ void intersect_spheres(const Ray &r, float radiusA, float radiusB, bool &hitA,
                                                   float &nearA, float &farA, bool &hitB, float &nearB,
                                                   float &farB) {
@@ -117,10 +155,13 @@ __device__ __forceinline__ void intersect_spheres(const Ray &r, float radiusA, f
     d = sqrtf(d);
     const float q = B < 0.f ? -0.5f * (B - d) : -0.5f * (B + d);
     float t1, t2;
-    if (okA && recip_ok(q)) {
-      t1 = div_recip(q, rA);
-      t2 = div_recip(C, recip_d(q));
-    } else {
+    bool fast = okA && recip_ok(q);
+    if (fast) {
+      t1 = div_product(q, rA);
+      t2 = div_product(C, recip_d(q));
+      fast = ((int)div_unsettled(t1) | (int)div_unsettled(t2)) == 0;
+    }
+    if (__builtin_expect(!fast, 0)) {
       t1 = q / A;
       t2 = C / q;
     }
@@ -135,6 +176,10 @@ __device__ __forceinline__ void intersect_spheres(const Ray &r, float radiusA, f
 // intersect_spheres for a ray of an interior packet (host/irt_void.cpp section 4: both discriminants
 // are >= 0 and recip_ok holds for A and both q): the same expressions in the same order on the
 // recip_d path alone -- no d < 0 exit, no guard, no fallback division -- so every bit is the same.
+// No subnormal test either: the certificate's eye lies more than 1.001 outer radii R from the
+// centre (irt_void.cpp section 1), the quotients are the ray's distances to the two spheres, at
+// least 0.001 R less their float error (a few 2^-19 of the eye's distance), so normal floats for
+// every R above ~1e-34 -- and a product that is a normal float is the division's.
 __device__ __forceinline__ void intersect_spheres_interior(const Ray &r, float radiusA, float radiusB, float &nearA,
                                                            float &farA, float &nearB, float &farB) {
   const float A = dot3(r.dx, r.dy, r.dz, r.dx, r.dy, r.dz);
@@ -145,8 +190,8 @@ __device__ __forceinline__ void intersect_spheres_interior(const Ray &r, float r
     const float C = OO - radius * radius;
     const float d = sqrtf(B * B - 4.f * A * C);
     const float q = B < 0.f ? -0.5f * (B - d) : -0.5f * (B + d);
-    const float t1 = div_recip(q, rA);
-    const float t2 = div_recip(C, recip_d(q));
+    const float t1 = div_product(q, rA);
+    const float t2 = div_product(C, recip_d(q));
     tnear = fminf(t1, t2);
     tfar = fmaxf(t1, t2);
   };
@@ -159,18 +204,25 @@ __device__ __forceinline__ int project_axis(float s, float lo, float hi, int dim
   return f2i_x86((s - lo) / (hi - lo) * (float)(dim - 1));
 }
 
-// a / b, correctly rounded, for a divisor b fixed per launch, given invB = 1 / (double)b:
+// a / b as the f32 division rounds it, for a divisor b fixed per launch, given invB = 1 / (double)b:
 // one double product rounded to float.  The product is within 2^-52 (relative) of a/b,
 // while a quotient of two floats that is not itself a float midpoint lies at least ~2^-49
-// (relative) from every midpoint between floats -- and is never exactly one -- so both round
-// to the same float.  b = 0, inf, NaN give 0/0 = NaN, a/0 = +-inf, a/inf = +-0 either way.
-// Replaces the ~10-instruction correctly rounded f32 division sequence.
-__device__ __forceinline__ float div_uniform(float a, double invB) {
-  return (float)((double)a * invB);
+// (relative) from every midpoint between NORMAL floats -- and is never exactly one -- so both round
+// to the same float.  Between subnormal floats a quotient can be an exact midpoint (see div_recip):
+// a product that comes out subnormal is redone by the division, which is why the divisor comes
+// along.  b = 0, inf, NaN give 0/0 = NaN, a/0 = +-inf, a/inf = +-0 either way.
+// Replaces the ~10-instruction f32 division sequence wherever the quotient is a normal float.
+__device__ __forceinline__ float div_uniform(float a, double invB, float b) {
+  const float f = div_product(a, invB);
+  if (__builtin_expect(div_unsettled(f), 0)) return a / b;
+  return f;
 }
-// project_axis with the per-launch 1 / (double)(hi - lo)
+// project_axis with the per-launch 1 / (double)(hi - lo).  The bare product: a subnormal quotient,
+// whichever of two neighbouring subnormals it is, times dim - 1 < 2^31 stays below 2^-95 and
+// converts to cell 0 either way (tests/test_gpu_raymath.py test_project_axis_on_subnormal_ties
+// holds the cell to the oracle's on such ties).
 __device__ __forceinline__ int project_axis_inv(float s, float lo, double invSize, int dim) {
-  return f2i_x86(div_uniform(s - lo, invSize) * (float)(opaque_u(dim) - 1));
+  return f2i_x86(div_product(s - lo, invSize) * (float)(opaque_u(dim) - 1));
 }
 
 // normalizeGridCoord (ShellAccel.h:71-80): the while-loops compute c mod d in [0,d).  A

@@ -60,9 +60,12 @@ __device__ __forceinline__ void gen_ray(const RenderArgs &A, int accumID, int x,
   const float len = sqrtf(dot3(dx, dy, dz, dx, dy, dz));
   if (recip_ok(len)) {  // normalize's three quotients through one reciprocal (irt_device.h)
     const double r = recip_d(len);
-    dx = div_recip(dx, r);
-    dy = div_recip(dy, r);
-    dz = div_recip(dz, r);
+    // (the bare products: one that comes out subnormal, where alone the division may round
+    // otherwise, is below 1e-5 whichever neighbour it is, and the clamp below overwrites it:
+    // tests/raymath_cases.py gen_ray_tie_cases)
+    dx = div_product(dx, r);
+    dy = div_product(dy, r);
+    dz = div_product(dz, r);
   } else {
     dx = dx / len;
     dy = dy / len;

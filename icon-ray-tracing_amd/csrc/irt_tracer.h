@@ -761,7 +761,7 @@ struct Tracer : std::conditional_t<(OPT & OPT_TIMING) != 0, TimeAccOn, TimeAccOf
   // from post_classify on acceptance
   __device__ __forceinline__ float classify_alpha(float v) {
     const RenderArgs &LA = fresh_args();  // read where used
-    v = div_uniform(v - LA.tfLo, LA.invTf);  // (v - tfLo) / (tfHi - tfLo), correctly rounded
+    v = div_uniform(v - LA.tfLo, LA.invTf, LA.tfHi - LA.tfLo);  // (v - tfLo) / (tfHi - tfLo), as the division rounds it
     const int size = opaque_u(LA.lutSize);
     const int idx = f2i_x86(v * (float)size);
     const float frac = (v * (float)size) - (float)idx;
@@ -775,7 +775,7 @@ struct Tracer : std::conditional_t<(OPT & OPT_TIMING) != 0, TimeAccOn, TimeAccOf
   // postClassify (deviceCode.cu:127-135): weights reversed, opacityScale on 2nd term only
   __device__ __forceinline__ float4 post_classify(float v) {
     const RenderArgs &LA = fresh_args();  // read where used
-    v = div_uniform(v - LA.tfLo, LA.invTf);  // (v - tfLo) / (tfHi - tfLo), correctly rounded
+    v = div_uniform(v - LA.tfLo, LA.invTf, LA.tfHi - LA.tfLo);  // (v - tfLo) / (tfHi - tfLo), as the division rounds it
     const int size = opaque_u(LA.lutSize);
     const int idx = f2i_x86(v * (float)size);
     const float frac = (v * (float)size) - (float)idx;

@@ -477,6 +477,58 @@ def box1(lo, hi) -> Box1:
     return Box1(float(lo), float(hi))
 
 
+# ------------------------------------------------- value-by-value device hooks (tests only)
+def debug_device_div(a: np.ndarray, b: np.ndarray, device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """irt_debug_device_div: (div_uniform, div_recip or the fallback division) of a / b."""
+    a = np.ascontiguousarray(a, dtype=np.float32).ravel()
+    b = np.ascontiguousarray(b, dtype=np.float32).ravel()
+    u, r = np.zeros(a.size, np.float32), np.zeros(a.size, np.float32)
+    L = lib()
+    L.irt_debug_device_div.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    _check(L.irt_debug_device_div(device, _ptr(a), _ptr(b), a.size, _ptr(u), _ptr(r)), "irt_debug_device_div")
+    return u, r
+
+
+def debug_ray_tests(rays: np.ndarray, interior: np.ndarray, box6, radius_a: float, radius_b: float,
+                    device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """irt_debug_ray_tests: (flags int32 (n,), out float32 (n, 14)) -- see include/icon_rt_hip_debug.h."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    interior = np.ascontiguousarray(interior, dtype=np.uint8).ravel()
+    box6 = np.ascontiguousarray(box6, dtype=np.float32).ravel()
+    flags = np.zeros(len(rays), np.int32)
+    out = np.zeros((len(rays), 14), np.float32)
+    L = lib()
+    L.irt_debug_ray_tests.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float,
+                                      C.c_void_p, C.c_void_p]
+    _check(L.irt_debug_ray_tests(device, _ptr(rays), _ptr(interior), len(rays), _ptr(box6), float(radius_a),
+                                 float(radius_b), _ptr(flags), _ptr(out)), "irt_debug_ray_tests")
+    return flags, out
+
+
+def debug_gen_ray(lp: "LaunchParams", width: int, height: int, device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """irt_debug_gen_ray: (dir float32 (H, W, 3), LCG state uint32 (H, W)) of gen_ray per pixel."""
+    d = np.zeros((height, width, 3), np.float32)
+    st = np.zeros((height, width), np.uint32)
+    L = lib()
+    L.irt_debug_gen_ray.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    _check(L.irt_debug_gen_ray(device, C.byref(lp), width, height, _ptr(d), _ptr(st)), "irt_debug_gen_ray")
+    return d, st
+
+
+def debug_grid_coord(s: np.ndarray, lo: float, hi: float, dim: int, c: np.ndarray, d: int,
+                     device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """irt_debug_grid_coord: (project_axis_inv of s, wrap_coord of c)."""
+    s = np.ascontiguousarray(s, dtype=np.float32).ravel()
+    c = np.ascontiguousarray(c, dtype=np.int32).ravel()
+    cell, wrapped = np.zeros(s.size, np.int32), np.zeros(c.size, np.int32)
+    L = lib()
+    L.irt_debug_grid_coord.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    _check(L.irt_debug_grid_coord(device, _ptr(s), s.size, float(lo), float(hi), dim, _ptr(cell), _ptr(c), c.size, d,
+                                  _ptr(wrapped)), "irt_debug_grid_coord")
+    return cell, wrapped
+
+
 # ----------------------------------------------------------------------- host helpers
 def default_kernel_id(ctx=None) -> int:
     """Template id of the raygen kernel (k_render<id>, as rocprofv3 names it) that `ctx`
@@ -1448,6 +1500,17 @@ class Context:
         _check(L.irt_debug_locate_sampler(self._h, int(mode), _ptr(pts), len(pts), _ptr(found),
                                           _ptr(value)), "irt_debug_locate_sampler")
         return found, value
+
+    def debug_classify(self, values: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """irt_debug_classify: the kernels' post_classify (n, 4) and classify_alpha (n,) of `values`
+        under the current transfer function."""
+        v = np.ascontiguousarray(values, dtype=np.float32).ravel()
+        out = np.zeros((v.size, 4), np.float32)
+        alpha = np.zeros(v.size, np.float32)
+        L = lib()
+        L.irt_debug_classify.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _check(L.irt_debug_classify(self._h, _ptr(v), v.size, _ptr(out), _ptr(alpha)), "irt_debug_classify")
+        return out, alpha
 
     def grid(self) -> tuple[np.ndarray, np.ndarray]:
         """GRID_ACCEL_MODE grid: (valueRanges (256^3, 2), maxOpacities (256^3,))."""

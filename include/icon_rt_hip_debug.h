@@ -142,6 +142,41 @@ int irt_debug_device_woodcock_log(int device, float *out);
 /* The kernels' make_8bit(linear_to_srgb(x[i])) (csrc/irt_device.h srgb_byte) for n host
  * values on GPU `device`; out: n bytes widened to uint32. */
 int irt_debug_device_srgb(int device, const float *x, uint32_t *out, int n);
+/* The raygen's per-value arithmetic, one value at a time on the device (csrc/irt_debug_raymath.hip;
+ * the kernels call the raygen's own inline functions).  Host arrays in and out, at most 2^18 values
+ * per call.
+ * irt_debug_device_div: outUniform[i] = div_uniform(a[i], 1 / (double)b[i], b[i]), the quotient by a
+ * per-launch divisor with the inverse computed on the host as a launch computes it; outRecip[i] =
+ * div_recip(a[i], b[i], recip_d(b[i])) where recip_ok(b[i]) holds and a[i] / b[i] otherwise, as the ray
+ * tests choose.  Both must equal the f32 division a[i] / b[i] bit for bit. */
+int irt_debug_device_div(int device, const float *a, const float *b, int n, float *outUniform, float *outRecip);
+/* Tracer::post_classify (out4[4i..4i+3]) and Tracer::classify_alpha (alpha[i]) of v[i] under the
+ * context's current transfer function (irt_set_transfunc; IRT_E_INVALID without one). */
+int irt_debug_classify(irt_context *ctx, const float *v, int n, float *out4, float *alpha);
+/* The ray tests on rays[6i..6i+5] = {org, dir} with tmin 0, tmax 1e10, the box box6 = {lower,
+ * upper} and the radii A and B.  flags[i]: the IRT_DEBUG_RAY_* bits; out14[14i..]: box_test's t0 t1,
+ * intersect_sphere's near far for A and for B, intersect_spheres' near far for A and B,
+ * intersect_spheres_interior's near far for A and B -- 0 where a test writes nothing (a sphere
+ * missed).  The interior form runs only where interior[i] != 0: the caller vouches for its
+ * precondition (both discriminants >= 0, recip_ok for dot(dir, dir) and both q). */
+enum {
+  IRT_DEBUG_RAY_BOX = 1,
+  IRT_DEBUG_RAY_SPHERE_A = 2,
+  IRT_DEBUG_RAY_SPHERE_B = 4,
+  IRT_DEBUG_RAY_SPHERES_A = 8,
+  IRT_DEBUG_RAY_SPHERES_B = 16,
+  IRT_DEBUG_RAY_INTERIOR = 32
+};
+int irt_debug_ray_tests(int device, const float *rays, const uint8_t *interior, int n, const float box6[6],
+                        float radiusA, float radiusB, int32_t *flags, float *out14);
+/* gen_ray for every pixel of a width x height frame with lp's camera and accumID: the direction
+ * (dir3[3p..3p+2], p = x + width y) and the LCG state after the two jitter draws (state[p]). */
+int irt_debug_gen_ray(int device, const irt_launch_params *lp, int width, int height, float *dir3,
+                      uint32_t *state);
+/* cell[i] = project_axis_inv(s[i], lo, 1 / (double)(hi - lo), dim) and wrapped[i] =
+ * wrap_coord(c[i], d); either list may be empty. */
+int irt_debug_grid_coord(int device, const float *s, int ns, float lo, float hi, int dim, int32_t *cell,
+                         const int32_t *c, int nc, int d, int32_t *wrapped);
 /* The render kernel's point location (sampleVolume over the context's binned lists,
  * csrc/irt_render.hip Tracer::locate) for n points xyz[3i..3i+2]: found[i] 0/1, value[i]. */
 int irt_debug_locate(irt_context *ctx, const float *xyz, int n, int *found, float *value);

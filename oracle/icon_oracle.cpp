@@ -1614,4 +1614,77 @@ void oracle_post_classify(const float *lut, int size, float lo, float hi, float 
   out4[0] = r.x; out4[1] = r.y; out4[2] = r.z; out4[3] = r.w;
 }
 
+// ---- batched forms for the value-by-value tests (tests/raymath_cases.py): one call per list
+void oracle_post_classify_n(const float *lut, int size, float lo, float hi, float opacityScale,
+                            const float *v, int n, float *out4) {
+  for (int i = 0; i < n; ++i) oracle_post_classify(lut, size, lo, hi, opacityScale, v[i], out4 + 4 * i);
+}
+// postClassify's intermediate values (deviceCode.cu:129-131): the quotient, idx and frac
+void oracle_classify_index_n(int size, float lo, float hi, const float *v, int n, float *quot,
+                             int32_t *idx, float *frac) {
+  for (int i = 0; i < n; ++i) {
+    const float t = (v[i] - lo) / (hi - lo);
+    quot[i] = t;
+    idx[i] = f2i(t * size);
+    frac[i] = (t * size) - idx[i];
+  }
+}
+// boxTest and intersectSphere for two radii on rays[6i..] = {org, dir}, tmin 0, tmax 1e10:
+// flags bit 0 box, 1 sphere A, 2 sphere B; out6 = t0 t1 nearA farA nearB farB (0 where a sphere is
+// missed); terms7 = dot(dir, dir), then per radius the discriminant, q and C of intersectSphere
+void oracle_ray_tests_n(const float *rays, int n, oc_box3 box, float rA, float rB, int32_t *flags,
+                        float *out6, float *terms7) {
+  for (int i = 0; i < n; ++i) {
+    const float *p = rays + 6 * (size_t)i;
+    Ray r{{p[0], p[1], p[2]}, 0.f, {p[3], p[4], p[5]}, 1e10f};
+    float *o = out6 + 6 * (size_t)i, *t = terms7 + 7 * (size_t)i;
+    for (int k = 0; k < 6; ++k) o[k] = 0.f;
+    int f = boxTest(r, toB3(box), o[0], o[1]) ? 1 : 0;
+    f |= intersectSphere(r, rA, o[2], o[3]) ? 2 : 0;
+    f |= intersectSphere(r, rB, o[4], o[5]) ? 4 : 0;
+    flags[i] = f;
+    const float A = dot(r.dir, r.dir), B = dot(r.dir, r.org) * 2.f;
+    t[0] = A;
+    const float rad[2] = {rA, rB};
+    for (int k = 0; k < 2; ++k) {
+      const float C = dot(r.org, r.org) - rad[k] * rad[k];
+      const float d = B * B - 4.f * A * C;
+      const float sq = sqrtf(d);
+      t[1 + 3 * k] = d;
+      t[2 + 3 * k] = B < 0.f ? -0.5f * (B - sq) : -0.5f * (B + sq);
+      t[3 + 3 * k] = C;
+    }
+  }
+}
+// generateRay for every pixel of a W x H frame as the raygen seeds it (deviceCode.cu:288-289):
+// the direction and the LCG state after the two draws
+void oracle_generate_ray_n(const float *camera12, int accumID, int W, int H, float *dir3, uint32_t *state) {
+  oc_params p{};
+  p.org = {camera12[0], camera12[1], camera12[2]};
+  p.dir_00 = {camera12[3], camera12[4], camera12[5]};
+  p.dir_du = {camera12[6], camera12[7], camera12[8]};
+  p.dir_dv = {camera12[9], camera12[10], camera12[11]};
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      LCG rnd((uint32_t)accumID * (uint32_t)W * (uint32_t)H + (uint32_t)x, (uint32_t)y);
+      const Ray r = generateRay(p, (float)x + .5f, (float)y + .5f, rnd);
+      const size_t q = (size_t)x + (size_t)W * y;
+      dir3[3 * q] = r.dir.x; dir3[3 * q + 1] = r.dir.y; dir3[3 * q + 2] = r.dir.z;
+      state[q] = rnd.state;
+    }
+}
+// projectToSphericalGrid's radial axis (ShellAccel.h:57-68) and normalizeGridCoord's (71-80)
+void oracle_grid_coord_n(const float *s, int ns, float lo, float hi, int dim, int32_t *cell,
+                         const int32_t *c, int nc, int d, int32_t *wrapped) {
+  const int dims[3] = {dim, 2, 2};
+  const B3 sb{{lo, 0.f, 0.f}, {hi, 1.f, 1.f}};
+  for (int i = 0; i < ns; ++i) cell[i] = projectToSphericalGrid({s[i], 0.f, 0.f}, dims, sb).x;
+  const int wd[3] = {d, 1, 1};
+  for (int i = 0; i < nc; ++i) wrapped[i] = normalizeGridCoord({c[i], 0, 0}, wd).x;
+}
+// a[i] / b[i], the f32 division
+void oracle_div_n(const float *a, const float *b, int n, float *out) {
+  for (int i = 0; i < n; ++i) out[i] = a[i] / b[i];
+}
+
 }  // extern "C"

@@ -187,6 +187,17 @@ void oracle_get_bounds(const oc_cell *cell, oc_box3 *out);                     /
 /* postClassify (deviceCode.cu:127-135) */
 void oracle_post_classify(const float *lut, int size, float lo, float hi, float opacityScale,
                           float v, float *out4);
+/* batched forms for the value-by-value tests (tests/raymath_cases.py) */
+void oracle_post_classify_n(const float *lut, int size, float lo, float hi, float opacityScale,
+                            const float *v, int n, float *out4);
+void oracle_classify_index_n(int size, float lo, float hi, const float *v, int n, float *quot,
+                             int32_t *idx, float *frac);
+void oracle_ray_tests_n(const float *rays, int n, oc_box3 box, float rA, float rB, int32_t *flags,
+                        float *out6, float *terms7);
+void oracle_generate_ray_n(const float *camera12, int accumID, int W, int H, float *dir3, uint32_t *state);
+void oracle_grid_coord_n(const float *s, int ns, float lo, float hi, int dim, int32_t *cell,
+                         const int32_t *c, int nc, int d, int32_t *wrapped);
+void oracle_div_n(const float *a, const float *b, int n, float *out);
 
 #ifdef __cplusplus
 }

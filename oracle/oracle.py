@@ -112,6 +112,12 @@ def olib() -> C.CDLL:
         L.oracle_to_cartesian.argtypes = [OVec3, C.POINTER(OVec3)]
         L.oracle_get_bounds.argtypes = [P, C.POINTER(OBox3)]
         L.oracle_post_classify.argtypes = [P, I, F, F, F, F, P]
+        L.oracle_post_classify_n.argtypes = [P, I, F, F, F, P, I, P]
+        L.oracle_classify_index_n.argtypes = [I, F, F, P, I, P, P, P]
+        L.oracle_ray_tests_n.argtypes = [P, I, OBox3, F, F, P, P, P]
+        L.oracle_generate_ray_n.argtypes = [P, I, I, I, P, P]
+        L.oracle_grid_coord_n.argtypes = [P, I, F, F, I, P, P, I, I, P]
+        L.oracle_div_n.argtypes = [P, P, I, P]
         _O = L
     return _O
 
@@ -157,6 +163,11 @@ def rlib() -> C.CDLL:
         L.ref_to_cartesian.argtypes = [P, P]
         L.ref_get_bounds.argtypes = [P, P]
         L.ref_generate_ray.argtypes = [P, I, I, C.c_uint, C.c_uint, P]
+        if hasattr(L, "ref_post_classify_n"):
+            L.ref_post_classify_n.argtypes = [P, I, F, F, F, P, I, P]
+            L.ref_ray_tests_n.argtypes = [P, I, P, F, F, P, P]
+            L.ref_generate_ray_n.argtypes = [P, I, I, I, P, P]
+            L.ref_div_n.argtypes = [P, P, I, P]
         _R = L
     return _R
 

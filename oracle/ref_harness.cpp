@@ -636,4 +636,50 @@ void ref_generate_ray(const float *camera12, int x, int y, unsigned s0, unsigned
   dir3[0] = r.dir.x; dir3[1] = r.dir.y; dir3[2] = r.dir.z;
 }
 
+// Batched known answers of the raygen's per-value arithmetic (tests/golden/kats_raymath.npz)
+void ref_post_classify_n(const float *lut, int size, float lo, float hi, float opacityScale, const float *v,
+                         int n, float *out4) {
+  RefParams lp;
+  lp.tfRange = box1f(lo, hi);
+  lp.opacityScale = opacityScale;
+  lp.lut = (const vec4f *)lut;
+  lp.lutSize = size;
+  for (int i = 0; i < n; ++i) {
+    const vec4f r = postClassify(lp, v[i]);
+    out4[4 * i] = r.x; out4[4 * i + 1] = r.y; out4[4 * i + 2] = r.z; out4[4 * i + 3] = r.w;
+  }
+}
+// flags bit 0 boxTest, 1 / 2 intersectSphere for rA / rB; out6 = t0 t1 nearA farA nearB farB (0 on a miss)
+void ref_ray_tests_n(const float *rays, int n, const float *box6, float rA, float rB, int *flags, float *out6) {
+  const box3f box(vec3f(box6[0], box6[1], box6[2]), vec3f(box6[3], box6[4], box6[5]));
+  for (int i = 0; i < n; ++i) {
+    const float *p = rays + 6 * (size_t)i;
+    Ray r(vec3f(p[0], p[1], p[2]), vec3f(p[3], p[4], p[5]), 0.f, 1e10f);
+    float *o = out6 + 6 * (size_t)i;
+    for (int k = 0; k < 6; ++k) o[k] = 0.f;
+    int f = boxTest(r, box, o[0], o[1]) ? 1 : 0;
+    f |= intersectSphere(r, rA, o[2], o[3]) ? 2 : 0;
+    f |= intersectSphere(r, rB, o[4], o[5]) ? 4 : 0;
+    flags[i] = f;
+  }
+}
+void ref_generate_ray_n(const float *camera12, int accumID, int W, int H, float *dir3, unsigned *state) {
+  RefParams lp;
+  lp.org = vec3f(camera12[0], camera12[1], camera12[2]);
+  lp.dir_00 = vec3f(camera12[3], camera12[4], camera12[5]);
+  lp.dir_du = vec3f(camera12[6], camera12[7], camera12[8]);
+  lp.dir_dv = vec3f(camera12[9], camera12[10], camera12[11]);
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      Random rnd((unsigned)accumID * (unsigned)W * (unsigned)H + (unsigned)x, (unsigned)y);
+      Ray r = generateRay(lp, vec2f(vec2i(x, y)) + vec2f(.5f), rnd);
+      const size_t q = (size_t)x + (size_t)W * y;
+      dir3[3 * q] = r.dir.x; dir3[3 * q + 1] = r.dir.y; dir3[3 * q + 2] = r.dir.z;
+      state[q] = rnd.state;
+    }
+}
+void ref_div_n(const float *a, const float *b, int n, float *out) {
+  for (int i = 0; i < n; ++i) out[i] = a[i] / b[i];
+}
+
 }  // extern "C"

@@ -696,9 +696,54 @@ def make_ragged_fixture():
     assert n <= 1 << 19, n
 
 
+def make_raymath_kats():
+    """kats_raymath.npz (`make_golden.py raymath` writes this file only): the reference build's answers on
+    the cases of tests/raymath_cases.py -- its f32 division on the division pairs (every
+    raymath_cases.KAT_STRIDE-th pair of each list), postClassify under every transfer function on the
+    thinned value lists (every edge case kept), boxTest / intersectSphere on the rays, generateRay per
+    pixel (16 x 16 whole, every seventh pixel of 67 x 33)."""
+    import raymath_cases as RC
+    R = O.rlib()
+    p = lambda a: a.ctypes.data  # noqa: E731
+    out = {}
+    for name, (a, b) in RC.div_pairs().items():
+        a, b = a[::RC.KAT_STRIDE[name]].copy(), b[::RC.KAT_STRIDE[name]].copy()
+        q = np.zeros(a.size, np.float32)
+        R.ref_div_n(p(a), p(b), a.size, p(q))
+        out.update({f"div_a_{name}": a, f"div_b_{name}": b, f"div_q_{name}": q})
+    for name, tf in RC.transfer_functions().items():
+        t, lo, hi, scale = tf
+        v = RC.classify_values(tf, thin=True)
+        o = np.zeros((v.size, 4), np.float32)
+        R.ref_post_classify_n(p(t), len(t), float(lo), float(hi), float(scale), p(v), v.size, p(o))
+        out.update({f"tf_lut_{len(t)}_{int(np.isnan(t).any())}": t, f"tf_range_{name}": np.float32([lo, hi, scale]), f"tf_v_{name}": v,
+                    f"tf_out_{name}": o})
+    for w in (False, True):
+        box, rA, rB = RC.ray_scene(w)
+        r = RC.rays(box, rA, rB)
+        fl, o = np.zeros(len(r), np.int32), np.zeros((len(r), 6), np.float32)
+        R.ref_ray_tests_n(p(r), len(r), p(box), float(rA), float(rB), p(fl), p(o))
+        out.update({f"ray_scene_{int(w)}": np.float32(list(box) + [rA, rB]), f"ray_rays_{int(w)}": r,
+                    f"ray_flags_{int(w)}": fl.astype(np.int8), f"ray_out_{int(w)}": o})
+    for name, cam, W, H, aid in RC.gen_ray_cases():
+        d, st = np.zeros((H, W, 3), np.float32), np.zeros((H, W), np.uint32)
+        R.ref_generate_ray_n(p(cam), aid, W, H, p(d), p(st))
+        step = 1 if W * H <= 256 else 7
+        out.update({f"gen_cam_{name}": cam, f"gen_dir_{name}": d.reshape(-1, 3)[::step].copy(),
+                    f"gen_state_{name}": st.ravel()[::step].copy()})
+    path = os.path.join(HERE, "kats_raymath.npz")
+    np.savez_compressed(path, **out)
+    n = os.path.getsize(path)
+    print(f"kats_raymath.npz: {n} bytes")
+    assert n <= 1 << 19, n
+
+
 if __name__ == "__main__":
     if not O.have_ref():
         sys.exit("oracle/_ref/libiconref.so missing: make -C oracle ref (needs /root/reference)")
+    if len(sys.argv) > 1 and sys.argv[1] == "raymath":
+        make_raymath_kats()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "ragged":
         make_ragged_fixture()
         sys.exit(0)
@@ -725,3 +770,4 @@ if __name__ == "__main__":
     make_terrain_fixtures()
     make_view_fixtures()
     make_ragged_fixture()
+    make_raymath_kats()

@@ -509,8 +509,12 @@ def test_lcg_jump_equals_sequential_steps():
 def test_division_by_a_launch_constant_as_one_double_product():
     """irt_device.h div_uniform: a / b correctly rounded to float equals the float rounding of
     (double)a * (1 / (double)b) -- the kernel's form for the per-launch divisors (transfer
-    function and shell-grid scale).  Random operands over many binades, the kernel's
-    operand ranges, and special values."""
+    function and shell-grid scale) -- with every product that comes out subnormal redone by
+    the division, as div_unsettled has it.  Random operands
+    over many binades, the kernel's operand ranges, special values, and the lists of
+    tests/raymath_cases.py: the exact subnormal ties (where the bare product is wrong, see
+    test_raymath_cpu.py) and the quotients 2^-48 from a normal-range midpoint."""
+    import raymath_cases as RC
     rng = np.random.default_rng(7)
     n = 4_000_000
     a = (rng.uniform(-1, 1, n) * 2.0 ** rng.integers(-60, 60, n)).astype(np.float32)
@@ -524,9 +528,10 @@ def test_division_by_a_launch_constant_as_one_double_product():
     sp = np.float32([0.0, -0.0, np.inf, -np.inf, np.nan, 1.0, 3.0, 1e-30, 7e30])
     a4, b4 = np.meshgrid(sp, sp)
     with np.errstate(all="ignore"):
-        for x, y in ((a, b), (a2, b2), (a3, b3), (a4.ravel(), b4.ravel())):
+        for x, y in ((a, b), (a2, b2), (a3, b3), (a4.ravel(), b4.ravel())) + tuple(RC.div_pairs().values()):
             ref = x / y  # float32 IEEE division
             got = (x.astype(np.float64) * (1.0 / y.astype(np.float64))).astype(np.float32)
+            got = np.where((np.abs(got) < RC.FLT_MIN) & (got != 0), ref, got)  # a subnormal product: a / b
             same = (ref.view(np.uint32) == got.view(np.uint32)) | (np.isnan(ref) & np.isnan(got))
             assert same.all(), (x[~same][:4], y[~same][:4])
 
@@ -534,7 +539,7 @@ def test_division_by_a_launch_constant_as_one_double_product():
 _RECIP_C = r"""
 #include <math.h>
 #include <stdint.h>
-/* irt_device.h recip_d / div_recip with the hardware estimate of 1/b replaced by the float
+/* irt_device.h recip_d / div_recip (the product, and the division where it comes out subnormal) with the hardware estimate of 1/b replaced by the float
    k ulps away from RN(1/b) (v_rcp_f32 is within 1 ulp); returns the mismatches vs a / b. */
 long check(const float *a, const float *b, long n, int k) {
   long bad = 0;
@@ -544,8 +549,9 @@ long check(const float *a, const float *b, long n, int k) {
     const double r0 = (double)r0f;
     const double e = fma(-(double)b[i], r0, 1.0);
     const double r = fma(r0, fma(e, e, e), r0);
-    const float got = (float)((double)a[i] * r);
+    float got = (float)((double)a[i] * r);
     const float ref = a[i] / b[i];
+    if (fabsf(got) < 0x1p-126f && got != 0.0f) got = a[i] / b[i];  /* div_unsettled: a subnormal product */
     if (!(got == ref || (isnan(got) && isnan(ref))) || signbit(got) != signbit(ref)) ++bad;
   }
   return bad;
@@ -558,7 +564,11 @@ def test_division_through_a_refined_reciprocal(tmp_path):
     correctly rounded equals (float)((double)a * r) with r the hardware reciprocal estimate
     refined once cubically in double -- for every estimate within 2 ulps of 1/b, random
     operands over the divisor range recip_ok admits (2^-100..2^100), the kernel's operand
-    shapes, quotients that overflow or land in the float subnormal range, and signed zeros."""
+    shapes, quotients that overflow or land in the float subnormal range, and signed zeros -- and,
+    of tests/raymath_cases.py, the exact subnormal ties and the quotients 2^-48 from a normal-range
+    midpoint whose divisors recip_ok admits.  Subnormal products are redone by the division
+    (div_unsettled), as the kernels do."""
+    import raymath_cases as RC
     import ctypes
     import subprocess
     src = tmp_path / "recip.c"
@@ -585,7 +595,13 @@ def test_division_through_a_refined_reciprocal(tmp_path):
     b4 = rng.uniform(-2e7, 2e7, n).astype(np.float32)
     a5 = np.float32([0.0, -0.0, 3.4e38, -3.4e38, 1e-45, 1e-38, 1.0, np.inf, np.nan])
     b5 = np.float32([1.0, 1.0, 2.0 ** -99, 2.0 ** -99, 2.0 ** 99, 2.0 ** 90, -(2.0 ** -100), 3.0, 3.0])
-    for x, y in ((a, b), (a2, b2), (a3, b3), (a4, b4), (a5, b5)):
+    extra = []
+    for name in ("ties", "ties_signed", "near_midpoints", "underflow", "subnormal"):
+        x, y = RC.div_pairs()[name]
+        ok = RC.recip_ok(y)
+        assert ok.sum() > x.size // 2, name
+        extra.append((x[ok], y[ok]))
+    for x, y in [(a, b), (a2, b2), (a3, b3), (a4, b4), (a5, b5)] + extra:
         x = np.ascontiguousarray(x, np.float32)
         y = np.ascontiguousarray(y, np.float32)
         for k in (-2, -1, 0, 1, 2):
