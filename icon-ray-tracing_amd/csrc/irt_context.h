@@ -238,6 +238,12 @@ struct irt_context {
   // Overlays (irt_overlay_create, irt_overlay.hip): the device objects this context owns, in the
   // order of their creation; irt_overlay_destroy takes one out, free_overlays the rest
   std::vector<irt_overlay *> overlays;
+  // Isolines (irt_contour_grid / irt_contour_latlon, irt_contour.hip): the passes' scratch on the
+  // device (tables, thresholds, counts, the packed per-cell counts, the per-workgroup totals), its
+  // pinned counterpart (the tables' staging and the counts' landing), and the value / found grid
+  // irt_contour_latlon samples into; each grows on demand, behind wait_samples
+  void *d_contour = nullptr, *h_contour = nullptr, *d_contourGrid = nullptr;
+  size_t contourCap = 0, contourHostCap = 0, contourGridCap = 0;  // bytes
   // streaming creation (irt_create_begin / _append / _end): the cells and their glibc
   // corner trig go to HBM chunk by chunk; the volume facts, column count and sphere
   // records are folded on the host in record order
@@ -303,6 +309,8 @@ hipError_t wait_samples(irt_context *c);  // waits for every sampling call alrea
 void free_sample_state(irt_context *c);   // after wait_samples: its events, tables and staging
 // irt_overlay.hip
 void free_overlays(irt_context *c);       // after wait_samples: every overlay the context still owns
+// irt_contour.hip
+void free_contour_state(irt_context *c);  // after wait_samples: the isoline passes' scratch
 
 namespace irt {
 // irt_launch.hip: what a frame's RenderArgs takes from the launch parameters, the transfer function

@@ -46,6 +46,14 @@
 //                                                a user exports from Natural Earth; none is shipped.  Lines
 //                                                are PX pixels wide at the sub-camera point (default 1.5),
 //                                                under the volume or, --lines-over, on top of it)
+//           [--contour R:c0,c1,... [--contour-grid NLAT,NLON]]
+//                                               (isolines of the field at radius R, metres from the
+//                                                centre, at the values c0, c1, ... (at most 16):
+//                                                irt_contour_latlon on a wrapped NLAT x NLON grid, pole to
+//                                                pole -- 361,720 by default, half a degree -- drawn through
+//                                                the same overlay, after the --graticule and --lines
+//                                                segments, --line-width wide.  The overlay then lies on the
+//                                                sphere of radius R, the level surface of --levels R)
 
 #include <math.h>
 #include <stdio.h>
@@ -93,6 +101,10 @@ struct AppState {  // hostCode.cu:65-92 (the parts this backend uses)
   float lineWidth = 1.5f;            // --line-width, pixels
   bool lineWidthGiven = false;
   bool linesOver = false;            // --lines-over
+  float contourRadius = 0.f;         // --contour R:c0,c1,...
+  std::vector<float> contour;        // ... the thresholds
+  bool contourGiven = false;
+  std::vector<float> contourGrid;    // --contour-grid: NLAT, NLON
 } g;
 
 void parseList(const std::string &list, std::vector<float> &out) {
@@ -162,6 +174,14 @@ void parseCommandLine(int argc, char *argv[]) {  // hostCode.cu:106-129
       g.lineWidth = strtof(argv[++i], nullptr), g.lineWidthGiven = true;
     else if (arg == "--lines-over")
       g.linesOver = true;
+    else if (arg == "--contour" && i + 1 < argc) {
+      const std::string v = argv[++i];
+      const size_t colon = v.find(':');
+      g.contourGiven = true;
+      g.contourRadius = strtof(v.substr(0, colon).c_str(), nullptr);
+      if (colon != std::string::npos) parseList(v.substr(colon + 1), g.contour);
+    } else if (arg == "--contour-grid" && i + 1 < argc)
+      parseList(argv[++i], g.contourGrid);
   }
 }
 
@@ -232,16 +252,24 @@ int main(int argc, char *argv[]) {
     }
   }
 
-  const bool lines = !g.graticule.empty() || !g.linesFile.empty();
+  if (g.contourGiven || !g.contourGrid.empty()) {
+    if (!g.contourGiven || g.contour.empty() || g.contour.size() > IRT_CONTOUR_MAX_THRESHOLDS ||
+        !(g.contourRadius > 0.f) || (!g.contourGrid.empty() && g.contourGrid.size() != 2)) {
+      fprintf(stderr, "icon_rt: --contour takes R:c0,c1,... (a positive radius, 1 to %d values); --contour-grid "
+                      "NLAT,NLON goes with it\n", IRT_CONTOUR_MAX_THRESHOLDS);
+      return -1;
+    }
+  }
+  const bool lines = !g.graticule.empty() || !g.linesFile.empty() || g.contourGiven;
   if (lines || g.linesOver || g.lineWidthGiven) {
     if (g.gpus > 0 || g.benchFrames > 0 || !g.section.empty() || g.histogram) {
-      fprintf(stderr, "icon_rt: --graticule and --lines draw into a frame on one device, without --bench, --section "
+      fprintf(stderr, "icon_rt: --graticule, --lines and --contour draw into a frame on one device, without --bench, --section "
                       "and --histogram\n");
       return -1;
     }
     if (!lines || (!g.graticule.empty() && g.graticule.size() != 2) || !(g.lineWidth > 0.f)) {
       fprintf(stderr, "icon_rt: --graticule takes latStepDeg,lonStepDeg; --line-width PX (positive) and --lines-over go "
-                      "with it or with --lines FILE\n");
+                      "with it, with --lines FILE or with --contour\n");
       return -1;
     }
   }
@@ -411,12 +439,13 @@ int main(int argc, char *argv[]) {
   // the camera's distance from the sphere, over its radius
   irt_overlay *overlay = nullptr;
   irt_vec4f *cover = nullptr;
-  const float surface = info.sphericalBounds.lower.x;
+  const float surface = g.contourGiven ? g.contourRadius : info.sphericalBounds.lower.x;
   if (lines) {
     const double rad = 3.14159265358979323846 / 180.0;
     float w = 0.f;
     if (irt_overlay_width(&lp, surface, g.lineWidth, &w)) die("irt_overlay_width");
-    const irt_overlay_style styles[2] = {{{1.f, 1.f, 1.f, 1.f}, w}, {{0.75f, 0.75f, 0.75f, 0.7f}, w}};
+    const irt_overlay_style styles[3] = {{{1.f, 1.f, 1.f, 1.f}, w}, {{0.75f, 0.75f, 0.75f, 0.7f}, w},
+                                         {{0.05f, 0.05f, 0.05f, 1.f}, w}};  // (2: the isolines)
     std::vector<irt_overlay_segment> seg;
     size_t nSeg = 0;
     const float maxArc = (float)rad;  // 1 degree pieces
@@ -441,7 +470,47 @@ int main(int argc, char *argv[]) {
       seg.resize(have + nSeg);
       if (irt_graticule(sLat, sLon, maxArc, 1, seg.data() + have, nSeg, &nSeg)) die("irt_graticule");
     }
-    if (irt_overlay_create(ctx, seg.data(), seg.size(), styles, 2, 0, &overlay)) die("irt_overlay_create");
+    if (g.contourGiven) {  // the isolines, on the device; they come last, so the others keep their indices
+      const double pi = 3.14159265358979323846;
+      const int numLat = g.contourGrid.empty() ? 361 : (int)g.contourGrid[0];
+      const int numLon = g.contourGrid.empty() ? 720 : (int)g.contourGrid[1];
+      if (numLat < 2 || numLon < 2) {
+        fprintf(stderr, "icon_rt: --contour-grid %d,%d: at least 2,2\n", numLat, numLon);
+        return -1;
+      }
+      std::vector<float> lat(numLat), lon(numLon);
+      for (int j = 0; j < numLat; ++j) lat[j] = (float)(-0.5 * pi + pi * (double)j / (double)(numLat - 1));
+      lat[0] = -(float)(0.5 * pi), lat[numLat - 1] = (float)(0.5 * pi);
+      for (int i = 0; i < numLon; ++i) lon[i] = (float)(-pi + 2.0 * pi * (double)i / (double)numLon);
+      const std::vector<int32_t> style(g.contour.size(), 2);
+      const int T = (int)g.contour.size();
+      size_t perT[IRT_CONTOUR_MAX_THRESHOLDS] = {};
+      if (irt_contour_latlon(ctx, lp.mode, lat.data(), numLat, lon.data(), numLon, g.contourRadius, g.contour.data(),
+                             style.data(), T, IRT_CONTOUR_WRAP, nullptr, 0, &nSeg, perT, nullptr))
+        die("irt_contour_latlon");
+      irt_overlay_segment *dSeg = nullptr;
+      const size_t have = seg.size();
+      if (nSeg) {
+        if (hipMalloc((void **)&dSeg, nSeg * sizeof(irt_overlay_segment)) != hipSuccess) {
+          fprintf(stderr, "icon_rt: no device memory for %zu isoline segments\n", nSeg);
+          return 1;
+        }
+        if (irt_contour_latlon(ctx, lp.mode, lat.data(), numLat, lon.data(), numLon, g.contourRadius, g.contour.data(),
+                               style.data(), T, IRT_CONTOUR_WRAP, dSeg, nSeg, &nSeg, perT, nullptr))
+          die("irt_contour_latlon");
+        seg.resize(have + nSeg);
+        // (the null stream's copy runs behind the emit pass)
+        if (hipMemcpy(seg.data() + have, dSeg, nSeg * sizeof(irt_overlay_segment), hipMemcpyDeviceToHost) != hipSuccess) {
+          fprintf(stderr, "icon_rt: copying the isoline segments back failed\n");
+          return 1;
+        }
+        (void)hipFree(dSeg);
+      }
+      fprintf(stderr, "icon_rt: isolines at radius %.9g on a %d x %d grid:", (double)g.contourRadius, numLat, numLon);
+      for (int t = 0; t < T; ++t) fprintf(stderr, " %.9g: %zu", (double)g.contour[t], perT[t]);
+      fprintf(stderr, " segments\n");
+    }
+    if (irt_overlay_create(ctx, seg.data(), seg.size(), styles, 3, 0, &overlay)) die("irt_overlay_create");
     // the line layer is lerped from the first frame on (0 * old at accumID 0): it starts cleared
     const size_t coverBytes = (size_t)fb.width * fb.height * sizeof(irt_vec4f);
     if (hipMalloc((void **)&cover, coverBytes) != hipSuccess || hipMemset(cover, 0, coverBytes) != hipSuccess) {

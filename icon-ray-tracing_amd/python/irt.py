@@ -159,6 +159,8 @@ OVERLAY_OVER = 1            # IRT_OVERLAY_OVER: the lines on top of the frame
 OVERLAY_MAX_HALF_WIDTH = 0.05
 OVERLAY_MAX_ARC = 0.2
 OVERLAY_MAX_BINS = 256
+CONTOUR_WRAP = 1            # IRT_CONTOUR_WRAP: the grid closes in longitude
+CONTOUR_MAX_THRESHOLDS = 16  # IRT_CONTOUR_MAX_THRESHOLDS
 
 
 def lib() -> C.CDLL:
@@ -217,6 +219,9 @@ def lib() -> C.CDLL:
             "irt_overlay_get_bins": [P, P, C.POINTER(I), C.POINTER(S)],
             "irt_overlay_width": [C.POINTER(LaunchParams), F, F, C.POINTER(F)],
             "irt_render_overlay": [P, P, C.POINTER(LaunchParams), I, I, F, I, P, P, P, P, P],
+            "irt_contour_cells": [P, P, P, I, P, I, P, P, I, I, P, S, C.POINTER(S), P],
+            "irt_contour_grid": [P, P, P, P, I, P, I, P, P, I, I, P, S, C.POINTER(S), P, P],
+            "irt_contour_latlon": [P, I, P, I, P, I, F, P, P, I, I, P, S, C.POINTER(S), P, P],
             "irt_debug_sample_admits": [F, F, F],
             "irt_clear_frame": [P, P, P, S, P],
             "irt_render": [P, C.POINTER(LaunchParams), I, I, P, P, P],
@@ -467,6 +472,57 @@ def overlay_width(lp: LaunchParams, height: int, surface_radius: float, pixels: 
     w = C.c_float()
     _check(lib().irt_overlay_width(C.byref(lp), float(surface_radius), float(pixels), C.byref(w)), "irt_overlay_width")
     return float(w.value)
+
+
+def _contour_args(lat, lon, thresholds, styles):
+    """A contour call's host arrays as the library takes them: lat, lon, thresholds float32, the
+    per-threshold style indices int32 (None: all 0; one int: that style for every threshold)."""
+    lat = np.ascontiguousarray(lat, dtype=np.float32).reshape(-1)
+    lon = np.ascontiguousarray(lon, dtype=np.float32).reshape(-1)
+    thr = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+    if styles is None or np.ndim(styles) == 0:
+        sty = np.full(thr.size, 0 if styles is None else int(styles), np.int32)
+    else:
+        sty = np.ascontiguousarray(styles, dtype=np.int32).reshape(-1)
+    if sty.size != thr.size:
+        raise IrtError(f"contour: {sty.size} styles for {thr.size} thresholds", E_INVALID)
+    return lat, lon, thr, sty
+
+
+class ContourError(IrtError):
+    """A contour call the library refused; count / counts hold what it had set (capacity < count)."""
+    def __init__(self, msg, code, count, counts):
+        super().__init__(msg, code)
+        self.count, self.counts = count, counts
+
+
+def _contour_check(rc: int, what: str, n, per):
+    if rc != 0:
+        msg = lib().irt_last_error().decode(errors="replace")
+        raise ContourError(f"{what} failed ({rc}): {msg}", rc, int(n.value), per.copy())
+
+
+def contour_cells(value, found, lat, lon, thresholds, styles=None, wrap: bool = False, return_counts: bool = False):
+    """irt_contour_cells, the isolines' definition on the host (no GPU): the isolines of value
+    (len(lat), len(lon)) float32 -- found: the same shape, uint8, or None -- at `thresholds`, as a
+    SEGMENT_DTYPE array ordered by threshold, then cell, then within the cell.  styles: the style
+    index per threshold.  return_counts: also the segments per threshold (int64)."""
+    lat, lon, thr, sty = _contour_args(lat, lon, thresholds, styles)
+    value = np.ascontiguousarray(value, dtype=np.float32)
+    if value.size != lat.size * lon.size:
+        raise IrtError(f"contour_cells: value of shape {value.shape} for a {lat.size} x {lon.size} grid", E_INVALID)
+    if found is not None:
+        found = np.ascontiguousarray(found, dtype=np.uint8)
+        if found.size != value.size:
+            raise IrtError(f"contour_cells: found of shape {found.shape} for value {value.shape}", E_INVALID)
+    n, per = C.c_size_t(), np.zeros(CONTOUR_MAX_THRESHOLDS, np.uintp)
+    args = (_ptr(value), _ptr(found) if found is not None else None, _ptr(lat), lat.size, _ptr(lon), lon.size,
+            _ptr(thr), _ptr(sty), thr.size, CONTOUR_WRAP if wrap else 0)
+    _contour_check(lib().irt_contour_cells(*args, None, 0, C.byref(n), _ptr(per)), "irt_contour_cells", n, per)
+    out = np.zeros(n.value, SEGMENT_DTYPE)
+    _contour_check(lib().irt_contour_cells(*args, _ptr(out), out.size, C.byref(n), _ptr(per)), "irt_contour_cells",
+                   n, per)
+    return (out, per[:thr.size].astype(np.int64)) if return_counts else out
 
 
 def vec3(v) -> Vec3:
@@ -1465,6 +1521,84 @@ class Context:
                                         int(height), float(surface_radius), OVERLAY_OVER if over else 0,
                                         C.c_void_p(accum_in_ptr), C.c_void_p(cover_ptr), C.c_void_p(fb_ptr),
                                         C.c_void_p(segment_ptr), C.c_void_p(stream)), "irt_render_overlay")
+
+    def contour_grid(self, value_ptr: int, found_ptr: int, lat, lon, thresholds, styles=None, out_ptr: int = 0,
+                     capacity: int = 0, wrap: bool = False, stream: int = 0):
+        """irt_contour_grid: the isolines of the device grid value_ptr (float32, len(lat) x len(lon))
+        / found_ptr (uint8; 0: every point found) at `thresholds`, written to the device array out_ptr
+        (64-byte aligned, `capacity` segments of SEGMENT_DTYPE) in the order of contour_cells, bit for
+        bit.  out_ptr 0 only counts.  Synchronises `stream` to read the counts; the segments are then
+        written in stream order.  Returns (count, counts per threshold int64); a refusal raises
+        ContourError, whose count / counts hold what the library had set."""
+        lat, lon, thr, sty = _contour_args(lat, lon, thresholds, styles)
+        n, per = C.c_size_t(), np.zeros(CONTOUR_MAX_THRESHOLDS, np.uintp)
+        _contour_check(lib().irt_contour_grid(self._h, C.c_void_p(value_ptr), C.c_void_p(found_ptr), _ptr(lat),
+                                              lat.size, _ptr(lon), lon.size, _ptr(thr), _ptr(sty), thr.size,
+                                              CONTOUR_WRAP if wrap else 0, C.c_void_p(out_ptr), int(capacity),
+                                              C.byref(n), _ptr(per), C.c_void_p(stream)), "irt_contour_grid", n, per)
+        return int(n.value), per[:thr.size].astype(np.int64)
+
+    def contour_latlon(self, lat, lon, radius: float, thresholds, styles=None, out_ptr: int = 0, capacity: int = 0,
+                       wrap: bool = False, mode: int = MODE_USER_GEOM, stream: int = 0):
+        """irt_contour_latlon: sample_latlon of the one level `radius` into a grid the context owns,
+        then contour_grid on it, on the same stream.  Returns (count, counts per threshold)."""
+        lat, lon, thr, sty = _contour_args(lat, lon, thresholds, styles)
+        n, per = C.c_size_t(), np.zeros(CONTOUR_MAX_THRESHOLDS, np.uintp)
+        _contour_check(lib().irt_contour_latlon(self._h, int(mode), _ptr(lat), lat.size, _ptr(lon), lon.size,
+                                                float(radius), _ptr(thr), _ptr(sty), thr.size,
+                                                CONTOUR_WRAP if wrap else 0, C.c_void_p(out_ptr), int(capacity),
+                                                C.byref(n), _ptr(per), C.c_void_p(stream)), "irt_contour_latlon",
+                       n, per)
+        return int(n.value), per[:thr.size].astype(np.int64)
+
+    def contour_segments(self, lat, lon, thresholds, styles=None, value=None, found=None, radius=None,
+                         wrap: bool = False, mode: int = MODE_USER_GEOM) -> np.ndarray:
+        """The isolines as a host SEGMENT_DTYPE array, computed on the device on torch's current
+        stream: of the torch tensors value / found (float32 / uint8, on the context's device) through
+        contour_grid, or, with radius, of the field at that level through contour_latlon."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if (value is None) == (radius is None):
+            raise IrtError("contour_segments: give either value or radius", E_INVALID)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if radius is None:
+                if value.device != dev or value.dtype != torch.float32 or not value.is_contiguous():
+                    raise IrtError(f"contour_segments: value must be contiguous float32 on {dev}", E_INVALID)
+                if value.numel() != np.size(lat) * np.size(lon):
+                    raise IrtError(f"contour_segments: value of {value.numel()} elements for a "
+                                   f"{np.size(lat)} x {np.size(lon)} grid", E_INVALID)
+                if found is not None and (found.device != dev or found.dtype != torch.uint8
+                                          or not found.is_contiguous() or found.numel() != value.numel()):
+                    raise IrtError(f"contour_segments: found must be contiguous uint8 on {dev}, as large as value",
+                                   E_INVALID)
+                call = lambda out, cap: self.contour_grid(  # noqa: E731
+                    value.data_ptr(), found.data_ptr() if found is not None else 0, lat, lon, thresholds, styles,
+                    out, cap, wrap, stream)
+            else:
+                call = lambda out, cap: self.contour_latlon(  # noqa: E731
+                    lat, lon, radius, thresholds, styles, out, cap, wrap, mode, stream)
+            n, _ = call(0, 0)
+            # (torch's allocations are 512-byte aligned: the 64-byte lines the kernel writes)
+            out = torch.empty((max(n, 1), SEGMENT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            if n:
+                call(out.data_ptr(), n)
+            host = out[:n].cpu().numpy()
+        return host.reshape(-1).view(SEGMENT_DTYPE).copy()
+
+    def contour_overlay(self, lat, lon, thresholds, styles, bins: int = 0, style_index=None, value=None,
+                        found=None, radius=None, wrap: bool = False, mode: int = MODE_USER_GEOM) -> "Overlay":
+        """A convenience: contour_segments (the device passes), copied back, as an overlay of this
+        context drawn in `styles` (overlay_styles' input); style_index: the style per threshold (None:
+        threshold k in style k modulo len(styles)); bins: the overlay's bins per edge (0: the
+        library's choice).  The returned Overlay's `segments` holds the host copy."""
+        styles = list(styles)
+        if style_index is None:
+            style_index = np.arange(np.size(thresholds)) % max(len(styles), 1)
+        seg = self.contour_segments(lat, lon, thresholds, style_index, value, found, radius, wrap, mode)
+        ov = self.overlay(seg, styles, bins)
+        ov.segments = seg
+        return ov
 
     def resample(self, points, mode: int = MODE_USER_GEOM, miss: float = float("nan")):
         """The field at `points` (..., 3): a float32 torch tensor on the context's device (sampled

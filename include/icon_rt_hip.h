@@ -603,6 +603,96 @@ int irt_render_overlay(irt_context *ctx, const irt_overlay *overlay, const irt_l
                        const irt_vec4f *d_accum_in, irt_vec4f *d_cover, uint32_t *d_fb,
                        int32_t *d_segment, void *stream);
 
+/* ---------------------------------------------------------------- isolines
+ * Isolines of a lat x lon value grid -- one level of irt_sample_latlon, one array of irt_column_out
+ * -- as overlay segments: marching squares on the sphere, from DEVICE values to a compact DEVICE
+ * array of irt_overlay_segment in a fixed order, ready for irt_overlay_create.  No counterpart in
+ * the reference.
+ *
+ * The definition (csrc/irt_contour.h, compiled by the host helper and by the kernels).  All arithmetic
+ * is double + - * / sqrt on float inputs, never an fma, evaluated left to right as written; the
+ * saddle's centre value alone is float.
+ *  - Inputs: value[j*numLon + i] and found[j*numLon + i] (found == NULL: every point is found);
+ *    lat[numLat], lon[numLon] float radians, strictly ascending, each step (the float difference of
+ *    neighbours) <= 0.1f rad, so that a cell's diagonal stays under the overlay's 0.2 rad arc limit;
+ *    numLat, numLon >= 2 and numLat * numLon < 2^27.  IRT_CONTOUR_WRAP: the grid closes in
+ *    longitude, numLon columns of cells instead of numLon - 1, the last between lon[numLon-1] and
+ *    lon[0]; legal only if, in double, lon[numLon-1] - lon[0] < 2 pi and the closing step 2 pi - that
+ *    span is <= 0.1f.  threshold[T], 1 <= T <= IRT_CONTOUR_MAX_THRESHOLDS, each finite, in any
+ *    order, repeats allowed; style[T] in [0, IRT_OVERLAY_MAX_STYLES), copied into the segments.
+ *  - Corner vectors: the host computes cos and sin of every lat and every lon once, in double, with
+ *    glibc (the axes of irt_latlon_points and irt_overlay_segments); the device receives the four
+ *    tables; a corner's unit vector is (cl*co, cl*si, sl).
+ *  - A cell (j, i) has corners 0 = (j, i), 1 = (j, i+1), 2 = (j+1, i+1), 3 = (j+1, i), i+1 modulo
+ *    numLon with wrap.  It emits nothing, for every threshold, if any corner is not found or not
+ *    finite.  Its edges, each always evaluated in this direction, so that the two cells sharing an
+ *    edge compute the same bits: e0 = 0 -> 1 (south), e1 = 1 -> 2 (east), e2 = 3 -> 2 (north),
+ *    e3 = 0 -> 3 (west).
+ *  - For threshold c: mask = sum over k of (v_k >= c) << k.  The crossing on an edge from corner A
+ *    to corner B: t = ((double)c - va) / ((double)vb - va); p = A + t*(B - A) per component;
+ *    P = p / sqrt((px*px + py*py) + pz*pz) per component.
+ *  - Segments per mask, first edge -> second edge (the side with value >= c lies on the left, seen
+ *    from outside with north up):  0, 15: none;  1: e0->e3;  2: e1->e0;  3: e1->e3;  4: e2->e1;
+ *    6: e2->e0;  7: e2->e3;  8: e3->e2;  9: e0->e2;  11: e1->e2;  12: e3->e1;  13: e0->e1;
+ *    14: e3->e0.  Saddles, with the centre value m = ((v0 + v1) + (v2 + v3)) * 0.25f in float:
+ *    mask 5: m >= c ? (e0->e1, e2->e3) : (e0->e3, e2->e1);  mask 10: m >= c ? (e1->e2, e3->e0) :
+ *    (e1->e0, e3->e2); in the order written.
+ *  - The segment from crossing Pa to crossing Pb (double), each field rounded once to float:
+ *    a = Pa, b = Pb; n = N / |N| with N = (Pa.y*Pb.z - Pa.z*Pb.y, Pa.z*Pb.x - Pa.x*Pb.z,
+ *    Pa.x*Pb.y - Pa.y*Pb.x); t = D / |D| with D = Pb - Pa; sinHalf = 0.5 * |D| (half the chord of two
+ *    unit vectors is the sine of half the arc); |v| = sqrt((vx*vx + vy*vy) + vz*vz); style =
+ *    style[T index], pad = 0.  A segment whose a and b are equal as floats in all three components is
+ *    DROPPED (a crossing at a shared corner; collapsed pole rows) and counts nowhere.
+ *  - Output order: threshold index (the caller's order), then cell index j*numCellsLon + i, then the
+ *    order within the cell.  The overlay's "lowest index wins" and d_segment picking depend on it.
+ *
+ * irt_contour_cells: the definition on the host, no GPU.  *count = the segments; countPerThreshold
+ * (T entries, may be NULL) their number per threshold.  out == NULL only counts; capacity < *count is
+ * IRT_E_INVALID with *count (and countPerThreshold) set.  IRT_E_INVALID, nothing written: an input
+ * outside the conditions above, a NULL value, lat, lon, threshold, style or count, unknown flag bits,
+ * 2^24 segments or more (the overlay's limit).
+ *
+ * irt_contour_grid: the same on the device, bit for bit and in the same order on every run.  d_value
+ * and d_found (may be NULL) are DEVICE arrays read on `stream`; lat, lon, threshold and style are HOST
+ * arrays, copied before the call returns; d_out is a DEVICE array of `capacity` segments, 64-byte
+ * aligned (refused otherwise), each segment written as one whole 64-byte line.  Three passes without
+ * a global atomic: count (one lane per cell, the kept segments of every threshold, per-workgroup
+ * totals from wave ballots), an exclusive scan of the totals in (threshold, workgroup) order, and
+ * emit (each lane's place from the scanned total and a wave prefix; the lane runs the definition
+ * again).  The counts are returned on the host, so THE CALL SYNCHRONISES `stream` after the first two
+ * passes; the emit pass is then queued on `stream`, and d_out is valid in stream order like any
+ * sampling call's output.  d_out == NULL counts only (no third pass); capacity < *count is
+ * IRT_E_INVALID with *count set and no byte of d_out written.  The scratch (4 bytes per cell, 4 bytes
+ * per threshold and 256 cells, the tables) belongs to the context, grows on demand and is freed by
+ * irt_destroy.  A sampling call in every respect of "resampling" above (the cell mode's checks):
+ * ordering, no launch-ring slot, no statistics, no IRT_E_CHAIN, refused while an update is pending.
+ * IRT_E_INVALID, nothing written: what irt_contour_cells refuses, a NULL or still-building context, a
+ * NULL d_value, a d_out that is not 64-byte aligned.
+ *
+ * irt_contour_latlon: irt_sample_latlon(mode, lat, lon, {radius}) with missValue NaN into a grid the
+ * context owns, then irt_contour_grid on it, on the same stream: equal, bit for bit, to the two calls
+ * made by hand.  Also refused: a radius that is not finite and positive, and what irt_sample_latlon
+ * refuses for `mode`.
+ *
+ * Not here: joining segments into polylines, labels, smoothing, building the overlay's bin table on
+ * the device (irt_overlay_create builds it on the host from a host copy of the segments), tile and
+ * multi-GPU forms. */
+#define IRT_CONTOUR_WRAP 1
+#define IRT_CONTOUR_MAX_THRESHOLDS 16
+int irt_contour_cells(const float *value, const uint8_t *found, const float *lat, int numLat,
+                      const float *lon, int numLon, const float *threshold, const int32_t *style,
+                      int numThresholds, int flags, irt_overlay_segment *out, size_t capacity,
+                      size_t *count, size_t *countPerThreshold);
+int irt_contour_grid(irt_context *ctx, const float *d_value, const uint8_t *d_found,
+                     const float *lat, int numLat, const float *lon, int numLon,
+                     const float *threshold, const int32_t *style, int numThresholds, int flags,
+                     irt_overlay_segment *d_out, size_t capacity, size_t *count,
+                     size_t *countPerThreshold, void *stream);
+int irt_contour_latlon(irt_context *ctx, int mode, const float *lat, int numLat, const float *lon,
+                       int numLon, float radius, const float *threshold, const int32_t *style,
+                       int numThresholds, int flags, irt_overlay_segment *d_out, size_t capacity,
+                       size_t *count, size_t *countPerThreshold, void *stream);
+
 /* == clearFramebuffer (common/pipeline.cu:171-199): fb = make_rgba(0), accum = 0. */
 int irt_clear_frame(irt_context *ctx, uint32_t *d_fb, irt_vec4f *d_accum, size_t numPixels,
                     void *stream);
